@@ -9,6 +9,12 @@ complete, Merkle-verified model (141 GB of bf16 weights in 30 safetensors shards
     --RCCL / IPC over xGMI--> every other GPU, which BLAKE3-hashes what it received as each round
     lands; GPU Merkle file hashes on every rank against the published ones.
 
+A plain run (`python bench.py --gpus N --steps K --warmup W`) sets up the bf16 world, warms up, times
+the K steps and prints the result line.  --full adds everything else the benchmark measures: the
+second data mode, after each mode the public-path row (zest_amd.parallel.swarm_pull on the same
+world, extra.swarm_pull_*) and a host spot check of the GPU chunk hashes.  --dump-outputs DIR writes
+what the last timed step left on rank 0 as DIR/<name>.npy (see dump_outputs).
+
 Data modes (--modes, first = the headline `value`, the others are reported under `extra`):
   bf16    N(0, 0.02) bf16 weights stored the way Xet stores real checkpoints: BG4-LZ4 chunk frames
           when smaller than the chunk (stored/raw ~0.88), so every step decodes them on the GPU.
@@ -24,7 +30,8 @@ as one rank.  At N > 1 a watchdog bounds every phase (faulthandler stack dump, t
 process group has an explicit timeout, so a stuck collective ends the run with a stack instead of
 an empty record.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model llama-3.1-70b] [--modes bf16,random]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--model llama-3.1-70b] [--modes bf16,random]
 """
 from __future__ import annotations
 
@@ -70,8 +77,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--model", default="llama-3.1-70b")
-    ap.add_argument("--modes", default=",".join(MODES),
-                    help="comma list of data modes; the first is the headline value, the rest go in extra")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: every data mode (--modes defaults to "
+                         f"{','.join(MODES)}), the public-path swarm_pull row after each mode (--swarm-row auto) and "
+                         "the host spot check of the GPU chunk hashes.  Without it a run measures one data mode only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step of the headline mode left on rank 0 as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of the arena and of the chunk hashes)")
+    ap.add_argument("--modes", default=None,
+                    help="comma list of data modes; the first is the headline value, the rest go in extra "
+                         f"(default {MODES[0]}; with --full {','.join(MODES)}; more than one implies --full)")
     ap.add_argument("--mode", default=None, choices=list(MODES), help="single data mode (= --modes MODE)")
     ap.add_argument("--round-mb", type=int, default=1024, help="per-rank bytes per pipeline round")
     ap.add_argument("--slots", type=int, default=4)
@@ -84,7 +99,8 @@ def parse_args(argv=None):
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: gloo rehearsal of the whole bench on host memory (tests; not a GPU number)")
     ap.add_argument("--swarm-row", default="auto", choices=["auto", "on", "off"],
-                    help="also time the PUBLIC path, zest_amd.parallel.swarm_pull (= pull(device='all')), on the "
+                    help="(part of --full: off without it, and `on` implies --full) also time the PUBLIC path, "
+                         "zest_amd.parallel.swarm_pull (= pull(device='all')), on the "
                          "last data mode's world, its CDN served from the same pinned origin through an "
                          "in-process memory CAS (mem:// fetch_info URLs, no sockets); reported under "
                          "extra.swarm_pull_*.  auto: on for GPU runs (at N > 1 a failure or overrun of the row is "
@@ -92,10 +108,16 @@ def parse_args(argv=None):
     ap.add_argument("--swarm-steps", type=int, default=2)
     ap.add_argument("--swarm-warmup", type=int, default=1)
     a = ap.parse_args(argv)
+    if a.swarm_row == "on" or (a.modes and "," in a.modes.strip(",")):
+        a.full = True  # asking for what only --full measures turns it on
+    if a.modes is None:
+        a.modes = ",".join(MODES if a.full else MODES[:1])
     a.modes = [a.mode] if a.mode else [m for m in a.modes.split(",") if m]
     bad = [m for m in a.modes if m not in MODES]
     if bad or not a.modes:
         ap.error(f"--modes: unknown {bad}; choose from {list(MODES)}")
+    if not a.full:  # a plain run does only what its headline figure needs
+        a.swarm_row = "off"
     return a
 
 
@@ -196,9 +218,53 @@ class Watchdog:
 # ------------------------------------------------------------------------------------------------
 # One rank
 # ------------------------------------------------------------------------------------------------
-def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=None, arenas=None, keep=None) -> dict:
+def dump_outputs(out_dir: str, puller, arena) -> None:
+    """--dump-outputs: what a caller of DevicePuller.step() holds after the last timed step, as
+    float32 .npy files (byte values are exact in float32).  The arena and the chunk-hash table of a
+    large model are sampled at positions drawn from a fixed seed, so two runs with the same
+    arguments write the same positions (arena_offsets.npy / chunk_rows.npy, float64):
+
+      arena.npy         arena bytes: all of them up to 8 MiB, else 2048 windows of 4096 bytes
+      chunk_hashes.npy  BLAKE3 chunk hashes the step computed on this rank [rows, 32]
+      file_hashes.npy   Merkle file hashes of the step [files, 32]
+      err.npy           the step's error word (0 = every hash matched)"""
+    import numpy as np
+    import torch
+
+    from zest_amd import ops
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(0x5EED)
+    win, n_win, rows = 4096, 2048, 65536
+    n = arena.numel()
+    if n <= win * n_win:
+        offs = torch.zeros(1, dtype=torch.int64)
+        sample = arena
+    else:
+        offs = torch.sort(torch.randint(0, n - win, (n_win,), generator=g)).values
+        idx = (offs[:, None] + torch.arange(win)[None, :]).to(arena.device)
+        sample = arena[idx]
+    n_chunks = puller.hashes.shape[0]
+    if n_chunks <= rows:
+        pick = torch.arange(n_chunks)
+    else:
+        pick = torch.sort(torch.randperm(n_chunks, generator=g)[:rows]).values
+    roots = getattr(puller, "roots", None)
+    if roots is None:  # host rehearsal: step() compares the roots without keeping them
+        roots = ops.merkle_roots(puller.hashes, puller.sizes, puller.jobs)
+    out = {"arena": sample.to(torch.float32), "arena_offsets": offs.to(torch.float64),
+           "chunk_hashes": puller.hashes[pick.to(puller.hashes.device)].to(torch.float32),
+           "chunk_rows": pick.to(torch.float64), "file_hashes": roots.to(torch.float32),
+           "err": puller.err.to(torch.float64)}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
+def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=None, arenas=None, keep=None,
+             dump_dir=None) -> dict:
     """Build the synthetic world of one data mode, pull it a.warmup + a.steps times; returns the
-    measured numbers (every rank) plus the puller's exchange choice."""
+    measured numbers (every rank) plus the puller's exchange choice.  dump_dir: rank 0 writes the
+    last timed step's outputs there (dump_outputs)."""
     import numpy as np
     import torch
 
@@ -222,6 +288,21 @@ def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=No
     log(rank, f"[{mode}] model {spec.repo_id}: {world.model_bytes / 1e9:.2f} GB in {len(world.xet_files)} files; "
               f"arena {world.arena_bytes / 1e9:.2f} GB; ranks {world_size}")
     contents = None
+    pin = None
+    if comp == "bg4" and world_size == 1:
+        # One rank, compressed world: the origin's pinned memory is taken on a thread of its own while
+        # this one allocates and fills the arena (pinning ~141 GB takes about a second).
+        from zest_amd.engine import pinned_take
+
+        pinned: list = []
+
+        def _pin():
+            torch.cuda.set_device(device)
+            t_pin = time.time()
+            pinned.append(pinned_take(int(world.model_bytes * 1.002) + (256 << 20)))
+            phase["pin_s"] = round(time.time() - t_pin, 3)
+        pin = threading.Thread(target=_pin, name="zest-pin")
+        pin.start()
     if cuda:
         # One arena for every data mode (the layout depends only on the model's files): freeing and
         # re-allocating 141 GB between modes is avoidable churn in the HBM allocator.
@@ -250,17 +331,22 @@ def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=No
                 if arenas is not None:
                     arenas["peers"] = mapped
                 log(rank, f"peer arenas mapped over HIP IPC before the build: {mapped is not None}")
+        t_gen = time.time()
         world.generate_on_device(arena)
+        torch.cuda.synchronize()
+        phase["generate_s"] = round(time.time() - t_gen, 3)
         # One rank, compressed world: the build's compression writes the serialized chunks straight
         # into pinned memory that becomes the origin (no second compression pass in build_origin).
         ser_store = None
-        if comp == "bg4" and world_size == 1:
-            from zest_amd.engine import pinned_take
-            cap, ptr = pinned_take(int(world.model_bytes * 1.002) + (256 << 20))
+        if pin is not None:
+            pin.join()
+            if not pinned:
+                raise SystemExit("pinning the origin failed")
+            cap, ptr = pinned[0]
             ser_store = (ptr, cap)
         # N > 1: each rank chunks / hashes / compresses only its files, then the plan is all-gathered
         world.build_on_device(arena, shard=(rank, world_size, None) if dist is not None else None,
-                              ser_store=ser_store)
+                              ser_store=ser_store, compress_batch=BUILD_COMPRESS_BATCH)
         torch.cuda.synchronize()
         if ser_store is not None and world.serialized is None:
             from zest_amd.engine import pinned_give
@@ -271,7 +357,7 @@ def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=No
     phase["world_s"] = round(time.time() - t_setup - phase.get("map_s", 0.0), 3)
     log(rank, f"[{mode}] xet plan: {world.n_chunks} chunks, {world.n_xorbs} xorbs, {len(world.terms)} terms "
               f"({time.time() - t_setup:.1f}s)")
-    if cuda:  # host oracle spot check of the GPU chunk hashes (8 chunks spread over the model)
+    if cuda and a.full:  # host oracle spot check of the GPU chunk hashes (8 chunks spread over the model)
         from zest_amd import _core
         for j in np.linspace(0, world.n_chunks - 1, 8).astype(int):
             o, n = int(world.chunk_off[j]), int(world.chunk_len[j])
@@ -374,6 +460,8 @@ def run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=No
     phase["timed_thread_cpu_s"] = _thread_cpu_delta(thr0, _thread_cpu(), top=6)
     wd.arm("report")
     puller.check()  # all timed steps verified (first error persists)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, puller, arena)
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=device)
     recv = torch.tensor([float(puller.bytes_received)], dtype=torch.float64, device=device)
     ing = torch.tensor([float(puller.bytes_ingested)], dtype=torch.float64, device=device)
@@ -925,7 +1013,17 @@ def topology(dist, device, world_size: int):
 HW_QUEUES = "8"
 
 
+# Chunks per compression launch of the world build (set-up, not the timed step).  Every batch costs a
+# device synchronise for its frame sizes, and the build compresses a batch's chunks longest first
+# (SyntheticWorld._build_file), which packs the CUs the better the larger the batch is.  70B bf16
+# set-up: 30.9-31.5 s with the build's default 8192 in chunk order, 28.7 s with 32768, 14.7 s with
+# 32768 longest first and the origin copy under the next batch.  The frames do not depend on the
+# batch or the order (each chunk is compressed on its own).
+BUILD_COMPRESS_BATCH = 32768
+
+
 def rank_main(a) -> None:
+    t_start = time.time()
     # Only when every rank has a GPU of its own: ranks sharing one GPU (the gloo rehearsal) would
     # stack 4 x 8 queues on one device, and the 4-rank rehearsal ran 133-150 GB/s with 8 queues per
     # rank against 186 with 4 (profiles/r4/rehearsal_r4d.log, rehearsal_n4_hwq8_r4l.log).
@@ -990,7 +1088,7 @@ def rank_main(a) -> None:
     for i, mode in enumerate(a.modes):
         keep = {} if swarm_row else None
         r = run_mode(a, mode, spec, device, rank, world_size, dist, wd, exchange_pick=pick, arenas=arenas,
-                     keep=keep)
+                     keep=keep, dump_dir=a.dump_outputs if i == 0 else None)
         pick = r["exchange"] if world_size > 1 else None
         log(rank, f"[{mode}] {r['value']:.3f} GB/s aggregate, {r['step_s'] * 1e3:.1f} ms/step, "
                   f"exchange {r['exchange']}")
@@ -1020,6 +1118,7 @@ def rank_main(a) -> None:
     if swarm_row:
         wd.arm("report")
     emit(_swarm_extra(swarm_rows, results))
+    log(rank, f"result line after {time.time() - t_start:.1f}s in this rank")
     # (the pinned origin pool is left to the process exit: unregistering ~141 GB one buffer at a time
     # only delays it)
     if dist is not None:

@@ -30,7 +30,7 @@ def _json_lines(text):
 
 @pytest.mark.parametrize("gpus", [1, 2])
 def test_bench_prints_one_json_line(gpus):
-    p, _ = _run(["--gpus", str(gpus), "--steps", "2", "--warmup", "1"])
+    p, _ = _run(["--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
     assert len(lines) == 1, p.stdout
@@ -50,6 +50,50 @@ def test_bench_prints_one_json_line(gpus):
         assert out["config"]["backend"] == "gloo" and 0 < out["p2p_ratio"] < 1
         assert "launching 2 ranks" in p.stderr
         assert sum(cfg["exchange_rx_GBps"]) > 0
+
+
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full: one data mode (bf16, the headline), no public-path row; --steps sets the
+    number of timed steps and ms_per_step is one of them; --dump-outputs writes the last step's
+    outputs as float arrays, the same from run to run."""
+    import numpy as np
+    dumps = []
+    for name, steps in (("a", 3), ("b", 2)):
+        d = tmp_path / name
+        p, _ = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = _json_lines(p.stdout)
+        assert len(lines) == 1, p.stdout
+        out = lines[0]
+        assert out["steps"] == steps and out["config"]["modes"] == ["bf16"] and out["dtype"] == "bf16"
+        assert set(out["extra"]) == {"bf16_GBps", "bf16_ms_per_step", "bf16_p2p_ratio", "bf16_stored_ratio"}
+        assert out["ms_per_step"] == pytest.approx(out["config"]["phase_s"]["timed_s"] * 1e3 / steps, rel=0.05, abs=0.5)
+        assert out["value"] == pytest.approx(out["config"]["model_bytes"] / out["ms_per_step"] / 1e6, rel=1e-2)
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert set(a) == {f"{n}.npy" for n in ("arena", "arena_offsets", "chunk_hashes", "chunk_rows", "file_hashes", "err")}
+    assert a.keys() == b.keys()
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["err.npy"].tolist() == [0.0] and a["chunk_hashes.npy"].shape[1] == 32 and a["arena.npy"].max() > 0
+
+
+def test_bench_extras_are_part_of_full():
+    """parse_args: a plain run has one data mode and no public-path row; --full has today's both
+    modes and the row on auto; asking for several modes or for the row turns --full on."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert (a.full, a.modes, a.swarm_row, a.steps, a.warmup, a.dump_outputs) == (False, ["bf16"], "off", 4, 2, None)
+    a = bench.parse_args(["--mode", "random"])
+    assert (a.full, a.modes, a.swarm_row) == (False, ["random"], "off")
+    a = bench.parse_args(["--full"])
+    assert (a.full, a.modes, a.swarm_row) == (True, ["bf16", "random"], "auto")
+    assert bench.parse_args(["--modes", "random,bf16"]).full and bench.parse_args(["--swarm-row", "on"]).full
+    assert bench.parse_args(["--swarm-row", "on"]).modes == ["bf16", "random"]
 
 
 def test_bench_one_seeder_one_leecher():
@@ -86,7 +130,7 @@ def test_bench_swarm_row_times_the_public_path(gpus):
     """--swarm-row on: after each engine mode, the same world is pulled through the public
     swarm_pull path from a mem:// memory CAS (every rank's pinned origin); extra.swarm_pull_* reports
     the first mode's row and swarm_pull_<mode>_* every mode's -- here on gloo CPU ranks."""
-    p, _ = _run(["--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--modes", "random,bf16", "--swarm-row", "on",
+    p, _ = _run(["--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full", "--modes", "random,bf16", "--swarm-row", "on",
                  "--swarm-steps", "2", "--swarm-warmup", "1"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -107,7 +151,7 @@ def test_bench_swarm_row_times_the_public_path(gpus):
 def test_bench_swarm_row_multi_file_three_ranks():
     """Three ranks on a 10-file model: the swarm row's term split matches the engine's per-rank
     origin shares (every rank's CDN fetches are served by its own memory CAS)."""
-    p, _ = _run(["--gpus", "3", "--steps", "1", "--warmup", "1", "--modes", "random", "--swarm-row", "on",
+    p, _ = _run(["--gpus", "3", "--steps", "1", "--warmup", "1", "--full", "--modes", "random", "--swarm-row", "on",
                  "--swarm-steps", "1", "--swarm-warmup", "1", "--model", "llama-tiny-sharded"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -121,7 +165,7 @@ def test_bench_swarm_row_multi_file_three_ranks():
 def test_bench_swarm_row_overrun_keeps_the_headline():
     """A rank that hangs inside the swarm row (after the headline was measured): the row's deadline
     prints the headline line once, with extra.swarm_pull_error, and every rank exits 0."""
-    p, dt = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--modes", "random", "--swarm-row", "on",
+    p, dt = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--modes", "random", "--swarm-row", "on",
                   "--swarm-steps", "1", "--swarm-warmup", "1"],
                  env_extra={"ZEST_BENCH_FAULT": "hang:1:swarm_timed", "ZEST_BENCH_WATCHDOG": "25"})
     assert p.returncode == 0, p.stderr[-3000:]

@@ -10,7 +10,8 @@
 #   kernels     HIP kernel numerics tests (tests/test_gpu_kernels.py)
 #   tests       full `pytest -m gpu` (one process)
 #   smoke       __graft_entry__.smoke()
-#   bench       default `python bench.py` (N=1, Llama-3.1-70B, bf16 headline + random) ($STEPS/$WARMUP)
+#   bench       `python bench.py --full` (N=1, Llama-3.1-70B, bf16 headline + random + public-path rows) ($STEPS/$WARMUP)
+#   plain       `python bench.py` as every change is measured: the bf16 headline alone ($STEPS/$WARMUP)
 #   rehearsal   self-launched `bench.py --gpus $RANKS` (default 2) on the one GPU (gloo control, ranks
 #               share the device; --exchange auto incl. the VMM-mapped ipc/xgmi modes), Llama-3.1-8B
 #   ipc         peer-mapped arena tests (tests/test_gpu_ipc.py)
@@ -54,9 +55,11 @@ for step in "$@"; do
            tail -1 $log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 || fail $step $? $log
            grep -h "smoke" $log ;;
-    bench) timeout -k 10 900 python -u bench.py --steps $STEPS --warmup $WARMUP > $log 2>&1 || fail $step $? $log
+    bench) timeout -k 10 900 python -u bench.py --full --steps $STEPS --warmup $WARMUP > $log 2>&1 || fail $step $? $log
            grep -h "aggregate" $log; tail -1 $log | cut -c1-400 ;;
-    rehearsal) ZEST_BENCH_BACKEND=gloo ZEST_BENCH_LOG_ALL=1 timeout -k 10 700 python -u bench.py --gpus ${RANKS:-2} \
+    plain) timeout -k 10 300 python -u bench.py --steps $STEPS --warmup $WARMUP > $log 2>&1 || fail $step $? $log
+           grep -h "aggregate" $log; tail -1 $log | cut -c1-400 ;;
+    rehearsal) ZEST_BENCH_BACKEND=gloo ZEST_BENCH_LOG_ALL=1 timeout -k 10 700 python -u bench.py --full --gpus ${RANKS:-2} \
                  --model llama-3.1-8b --steps 3 --warmup 1 ${REHEARSAL_ARGS:-} > $log 2>&1 || fail $step $? $log
                grep -h "mapped\|autotune\|GB/s aggregate" $log | head -12; tail -1 $log | cut -c1-600 ;;
     ipc) timeout -k 10 400 $PYT -v tests/test_gpu_ipc.py > $log 2>&1 || fail $step $? $log
@@ -82,7 +85,7 @@ for step in "$@"; do
               || fail $step $? $log
             grep -h kernel $OUT/kbench.jsonl | cut -c1-200 ;;
     prof) timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o b70 -- \
-            python3 bench.py --steps 3 --warmup 1 > $log 2>&1 || fail $step $? $log
+            python3 bench.py --full --steps 3 --warmup 1 > $log 2>&1 || fail $step $? $log
           db=$(find $OUT/prof -name "*.db" | head -1)
           python tools/rocpd_summary.py "$db" --title "70B bench kernels ($(git log -1 --format=%h 2>/dev/null || echo tree))" \
             > $OUT/kernels.md 2>&1
@@ -97,7 +100,7 @@ for step in "$@"; do
            db=$(find $OUT/gprof -name "*.db" | head -1)
            python tools/rocpd_summary.py "$db" --title "gpubench ${GPROF_MIB:-256} MiB kernels" > $OUT/kernels_gpubench.md 2>&1
            head -30 $OUT/kernels_gpubench.md; rm -f "$db" ;;
-    benchA|benchB) v=BENCH_ENV_${step#bench}; env ${!v:-} timeout -k 10 700 python -u bench.py --modes ${BENCH_MODES:-bf16} \
+    benchA|benchB) v=BENCH_ENV_${step#bench}; env ${!v:-} timeout -k 10 700 python -u bench.py --full --modes ${BENCH_MODES:-bf16} \
                 --steps $STEPS --warmup $WARMUP > $log 2>&1 || fail $step $? $log
               echo "env: ${!v:-}"; grep -h "aggregate" $log ;;
     gpubench) env ${GPUBENCH_ENV:-} timeout -k 10 500 python -u -m zest_amd.gpubench --json > $OUT/gpubench.json 2> $log \
@@ -122,7 +125,7 @@ for step in "$@"; do
           rm -rf $OUT/pmc ;;
     copytrace) # public-path swarm row under kernel + memory-copy + marker traces: does H2D overlap ingest?
                ZEST_BENCH_MARK=1 timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace \
-                 -d $OUT/ct -o ct -- python3 bench.py --model ${CT_MODEL:-llama-3.1-8b} \
+                 -d $OUT/ct -o ct -- python3 bench.py --full --model ${CT_MODEL:-llama-3.1-8b} \
                  --modes ${CT_MODES:-random} --steps 2 --warmup 1 --swarm-steps 2 --swarm-warmup 1 > $log 2>&1 \
                  || fail $step $? $log
                grep -h "aggregate" $log
@@ -135,7 +138,7 @@ for step in "$@"; do
                --model ${C2_MODEL:-llama-3.1-8b} --mode ${C2_MODE:-bf16} --ranks ${C2_RANKS:-2} \
                --out $OUT/config2.json > $log 2>&1 || fail $step $? $log
              python -c "import json,sys; d=json.load(open(sys.argv[1])); print({k: d[k] for k in ('aggregate_GBps','leecher_receive_GBps','cdn_bytes','backend')}, [(r['rank'], r['exchange'], r['from_cache'], r['received_bytes'], r['pull_s']) for r in d['per_rank']])" $OUT/config2.json ;;
-    swarmrow) timeout -k 10 600 python -u bench.py --model ${SR_MODEL:-llama-3.1-8b} --modes ${SR_MODES:-bf16,random} \
+    swarmrow) timeout -k 10 600 python -u bench.py --full --model ${SR_MODEL:-llama-3.1-8b} --modes ${SR_MODES:-bf16,random} \
                 --steps 5 --warmup 2 --swarm-steps 3 > $log 2>&1 || fail $step $? $log
               grep -h "GB/s aggregate\|swarm_pull" $log | cut -c1-300 ;;
     pmctable) # one counter group per rocprofv3 pass (SQ <= 8, TCC <= 4: FETCH_SIZE uses 3, WRITE_SIZE 2)

@@ -10,7 +10,7 @@ grep -E "PASSED|SKIPPED" gpurun_out/r5v/signals_unit.log
 bash tools/gpu/check.sh r5v ipc || exit 1
 run() {  # tag, env...
   local tag=$1; shift
-  env ZEST_BENCH_BACKEND=gloo "$@" timeout -k 10 400 python -u bench.py --gpus 2 --model llama-3.1-8b --modes bf16,random \
+  env ZEST_BENCH_BACKEND=gloo "$@" timeout -k 10 400 python -u bench.py --full --gpus 2 --model llama-3.1-8b --modes bf16,random \
     --steps 3 --warmup 1 > gpurun_out/r5v/$tag.log 2>&1 || { echo "[r5v] $tag failed"; tail -30 gpurun_out/r5v/$tag.log; exit 1; }
   echo "== $tag $*"; grep -h "GB/s aggregate" gpurun_out/r5v/$tag.log | grep -v "bench r1"
   tail -1 gpurun_out/r5v/$tag.log | python -c "import json,sys; d=json.JSONDecoder().raw_decode(sys.stdin.read())[0]; print({k: v for k, v in d['extra'].items() if 'wait' in k or 'ms_per' in k or 'signals' in k})"

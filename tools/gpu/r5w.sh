@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out/r5w
 export ZEST_SKIP_BUILD=1 TMPDIR=/tmp
 ZEST_BENCH_MARK=1 timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/r5w/ct -o ct -- \
-  python3 bench.py --model llama-3.1-70b --modes bf16 --steps 2 --warmup 1 --swarm-steps 2 --swarm-warmup 0 \
+  python3 bench.py --full --model llama-3.1-70b --modes bf16 --steps 2 --warmup 1 --swarm-steps 2 --swarm-warmup 0 \
   > gpurun_out/r5w/ct.log 2>&1 || { tail -30 gpurun_out/r5w/ct.log; exit 1; }
 grep -h "aggregate" gpurun_out/r5w/ct.log
 python tools/gpu/copy_rates.py gpurun_out/r5w/ct > gpurun_out/r5w/copy_rates.txt 2>&1; cat gpurun_out/r5w/copy_rates.txt

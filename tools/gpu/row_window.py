@@ -1,6 +1,6 @@
 """GPU activity inside the public-path row's timed window of a multi-rank rehearsal (every rank's
-process traced: rocprofv3 --kernel-trace --memory-copy-trace --output-format csv, bench.py run with
-ZEST_BENCH_MARK=1 so each rank brackets its timed calls with a sleep kernel).
+process traced: rocprofv3 --kernel-trace --memory-copy-trace --output-format csv, bench.py --full run
+with ZEST_BENCH_MARK=1 so each rank brackets its timed calls with a sleep kernel).
 
     python tools/gpu/row_window.py OUT_DIR
 

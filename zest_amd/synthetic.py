@@ -113,7 +113,8 @@ class SyntheticWorld:
             data = arena[f.arena_off + len(f.header):f.arena_off + f.size]
             ops.fill_synthetic(data, f.data_seed, 0, MODES[self.mode])
 
-    def build_on_device(self, arena: torch.Tensor, hash_batch: int = 1 << 20, shard=None, ser_store=None) -> None:
+    def build_on_device(self, arena: torch.Tensor, hash_batch: int = 1 << 20, shard=None, ser_store=None,
+                        compress_batch: int = 8192) -> None:
         """CDC + chunk hashes + file hashes (+ BG4-LZ4 stored sizes) + xorb/term plan, from content
         already in `arena`.
 
@@ -127,12 +128,18 @@ class SyntheticWorld:
         CAS serves it ([8-byte header | stored payload], chunk order) straight from this build's
         compression, so a one-rank origin (whose layout is exactly that: engine.DevicePuller, terms
         back to back) adopts the bytes instead of compressing every chunk a second time (compressed
-        worlds only; unsharded builds only).  On return `self.serialized` = (ptr, cap, nbytes)."""
+        worlds only; unsharded builds only).  On return `self.serialized` = (ptr, cap, nbytes).
+
+        compress_batch: chunks per compression launch (2 x LZ4_SLOT of device scratch per chunk);
+        the frames do not depend on it."""
         nf = len(self.xet_files)
         self.serialized = None
         self._ser_sink = None
         if ser_store is not None and self.compression == "bg4" and (shard is None or shard[1] == 1):
-            self._ser_sink = [int(ser_store[0]), int(ser_store[1]), 0, None]  # ptr, cap, written, tmp
+            # two packing buffers: batch k's copy to the store runs on a side stream under batch k+1's
+            # compression (`done` = the copy that last read each buffer)
+            self._ser_sink = {"ptr": int(ser_store[0]), "cap": int(ser_store[1]), "at": 0, "n": 0, "tmp": [None, None],
+                              "done": [None, None], "side": torch.cuda.Stream(arena.device)}
         if shard is None:
             own = list(range(nf))
         else:
@@ -140,7 +147,7 @@ class SyntheticWorld:
             rank, n_ranks, group = shard
             owner = assign_owners([f.size for f in self.xet_files], n_ranks)
             own = [i for i in range(nf) if owner[i] == rank]
-        per_file = {i: self._build_file(arena, i, hash_batch) for i in own}
+        per_file = {i: self._build_file(arena, i, hash_batch, compress_batch) for i in own}
         if shard is not None and shard[1] > 1:
             import torch.distributed as dist
             objs = [None] * shard[1]
@@ -148,8 +155,8 @@ class SyntheticWorld:
             for o in objs:
                 per_file.update(o)
         if self._ser_sink is not None:
-            ptr, cap, n, _ = self._ser_sink
-            self.serialized = (ptr, cap, n)
+            self._ser_sink["side"].synchronize()  # the last batches' copies have landed
+            self.serialized = (self._ser_sink["ptr"], self._ser_sink["cap"], self._ser_sink["at"])
             self._ser_sink = None
         parts = [per_file[i] for i in range(nf)]
         self._set_chunks(np.concatenate([p["offs"] for p in parts]), np.concatenate([p["lens"] for p in parts]),
@@ -161,7 +168,7 @@ class SyntheticWorld:
             self.chunk_scheme = np.concatenate([p["scheme"] for p in parts])
         self._plan_xorbs()
 
-    def _build_file(self, arena: torch.Tensor, i: int, hash_batch: int) -> dict:
+    def _build_file(self, arena: torch.Tensor, i: int, hash_batch: int, compress_batch: int = 8192) -> dict:
         """One Xet file on the GPU: CDC boundaries (K5), chunk hashes (K1), file hash (K2) and, for
         compressed worlds, every chunk's BG4-LZ4 stored size and scheme (frames discarded: the
         origin build compresses its own share again)."""
@@ -182,36 +189,54 @@ class SyntheticWorld:
         if self.compression == "bg4":
             clen = lens.astype(np.uint32).copy()
             scheme = np.zeros(len(lens), dtype=np.uint8)
-            for a in range(0, len(lens), 8192):
-                b = min(len(lens), a + 8192)
-                frames, flen = ops.compress_chunks(arena, offs[a:b], lens[a:b], bg4=True)
+            for a in range(0, len(lens), compress_batch):
+                b = min(len(lens), a + compress_batch)
+                # Longest chunks first: the compressor runs one wave per chunk and a block of four
+                # waves holds its LDS until its longest chunk is done, so chunks of like length share
+                # a block and the launch does not end behind a few long ones.  Chunk j's frame is in
+                # slot[j]; the frames themselves do not depend on the order.
+                order = np.argsort(-lens[a:b].astype(np.int64), kind="stable")
+                frames, flen_o = ops.compress_chunks(arena, offs[a:b][order], lens[a:b][order], bg4=True)
+                flen = np.empty_like(flen_o)
+                flen[order] = flen_o
+                slot = np.empty(len(order), dtype=np.uint64)
+                slot[order] = np.arange(len(order), dtype=np.uint64)
                 keep = flen > 0
                 clen[a:b][keep] = flen[keep]
                 scheme[a:b][keep] = 2
                 if self._ser_sink is not None:
-                    self._sink_frames(arena, frames, offs[a:b], lens[a:b], clen[a:b], scheme[a:b])
+                    self._sink_frames(arena, frames, slot, offs[a:b], lens[a:b], clen[a:b], scheme[a:b])
                 del frames
             out["clen"], out["scheme"] = clen, scheme
         return out
 
-    def _sink_frames(self, arena, frames, offs, lens, clen, scheme) -> None:
-        """Serialize one compressed batch ([header | frame or raw chunk] per chunk, compact) on the
-        GPU and append it to the pinned ser_store (D2H)."""
+    def _sink_frames(self, arena, frames, slot, offs, lens, clen, scheme) -> None:
+        """Serialize one compressed batch ([header | frame or raw chunk] per chunk, compact; chunk
+        j's frame in slot[j] of `frames`) on the GPU and append it to the pinned ser_store (D2H on
+        the side stream: the caller's next batch compresses meanwhile)."""
         ser = clen.astype(np.uint64) + np.uint64(8)
         total = int(ser.sum())
-        ptr, cap, at, tmp = self._ser_sink
-        if at + total > cap:
-            raise RuntimeError(f"ser_store too small: {at + total} > {cap} bytes")
+        s = self._ser_sink
+        if s["at"] + total > s["cap"]:
+            raise RuntimeError(f"ser_store too small: {s['at'] + total} > {s['cap']} bytes")
+        k = s["n"] % 2
+        main = torch.cuda.current_stream(arena.device)
+        if s["done"][k] is not None:
+            main.wait_event(s["done"][k])  # the copy of two batches ago has read this buffer
+        tmp = s["tmp"][k]
         if tmp is None or tmp.numel() < total:
-            tmp = ops.padded_empty(max(total, 1 << 30), arena.device)
-            self._ser_sink[3] = tmp
-        idx = np.arange(len(clen), dtype=np.uint64)
-        addr = np.where(scheme > 0, np.uint64(frames.data_ptr()) + idx * np.uint64(ops.LZ4_SLOT),
+            tmp = s["tmp"][k] = ops.padded_empty(max(total + total // 8, 1 << 30), arena.device)
+        addr = np.where(scheme > 0, np.uint64(frames.data_ptr()) + slot * np.uint64(ops.LZ4_SLOT),
                         np.uint64(arena.data_ptr()) + offs.astype(np.uint64))
         ops.pack_frames(addr, clen, lens, scheme, (np.cumsum(ser) - ser).astype(np.uint64), tmp)
-        ops.hip().memcpy_async(ptr + at, tmp.data_ptr(), total, torch.cuda.current_stream(arena.device).cuda_stream)
-        torch.cuda.synchronize(arena.device)  # tmp and frames are reused / freed next batch
-        self._ser_sink[2] = at + total
+        packed = torch.cuda.Event()
+        packed.record(main)
+        s["side"].wait_event(packed)
+        ops.hip().memcpy_async(s["ptr"] + s["at"], tmp.data_ptr(), total, s["side"].cuda_stream)
+        s["done"][k] = torch.cuda.Event()
+        s["done"][k].record(s["side"])
+        s["at"] += total
+        s["n"] += 1
 
     def pack_serialized(self, arena: torch.Tensor, a: int, b: int, out: torch.Tensor, out_off: np.ndarray) -> None:
         """Serialize chunks [a, b) ([8-byte header | stored payload], what the CAS serves) into `out`
