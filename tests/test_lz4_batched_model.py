@@ -22,9 +22,10 @@ WAVE = 64
 RING = 4096
 
 
-def parse_frame(frame: bytes):
+def parse_frame(frame: bytes, stats: dict | None = None):
     """LZ4 frame -> list of (literal_pos, literal_len, match_len, offset) records, literal runs split
-    at 0xFFFF and matches at 0x7FFF exactly like the kernel's emit()."""
+    at 0xFFFF and matches at 0x7FFF exactly like the kernel's emit().  stats["split_records"] counts
+    the records beyond one per sequence."""
     assert struct.unpack_from("<I", frame, 0)[0] == 0x184D2204
     flg = frame[4]
     ip = 7 + (8 if flg & 8 else 0) + (4 if flg & 1 else 0)
@@ -32,6 +33,12 @@ def parse_frame(frame: bytes):
     recs = []
 
     def emit(lp, lit, ml, off):
+        n0 = len(recs)
+        _emit(lp, lit, ml, off)
+        if stats is not None:
+            stats["split_records"] = stats.get("split_records", 0) + len(recs) - n0 - 1
+
+    def _emit(lp, lit, ml, off):
         while lit > 0xFFFF:
             recs.append((lp, 0xFFFF, 0, 0))
             lp += 0xFFFF
@@ -87,14 +94,108 @@ def parse_frame(frame: bytes):
     return recs
 
 
-def model_decode(frame: bytes, ulen: int, batch: int = WAVE) -> bytes:
-    recs = parse_frame(frame)
+FLUSH_ABOVE = WAVE - 8  # kFlushAbove: a batch holding more records than this is executed
+
+
+def kernel_batches(frame: bytes, stats: dict | None = None) -> list[int]:
+    """Record counts of the batches the one-wave parse (lz4seq.hip parse_frame) hands to exec_batch,
+    in order: its fast loop takes sequences without length bytes that start more than 18 bytes
+    before the block end, up to 64 records; the general path takes one sequence of any kind when the
+    batch holds at most FLUSH_ABOVE records.  stats["handover"] collects, per hand-over from the
+    fast loop to the general path, the distance from the sequence's token to the block end."""
+    flg = frame[4]
+    ip = 7 + (8 if flg & 8 else 0) + (4 if flg & 1 else 0)
+    bck = 4 if flg & 0x10 else 0
+    out = []
+    n = 0
+
+    def nrec(lit, ml):  # emit()
+        c = 0
+        while True:
+            l = min(lit, 0xFFFF)
+            m = 0 if lit > 0xFFFF else min(ml, 0x7FFF)
+            c += 1
+            lit -= l
+            ml -= m
+            if not (lit or ml):
+                return c
+
+    def chain(v, ip):
+        while True:
+            b = frame[ip]
+            ip += 1
+            v += b
+            if b != 255:
+                return v, ip
+
+    while True:
+        if n > FLUSH_ABOVE:
+            out.append(n)
+            n = 0
+        bs = struct.unpack_from("<I", frame, ip)[0]
+        ip += 4
+        if bs == 0:
+            break
+        ln = bs & 0x7FFFFFFF
+        if bs >> 31:
+            n += nrec(ln, 0)
+            ip += ln
+        else:
+            bend = ip + ln
+            while True:
+                if n > FLUSH_ABOVE:
+                    out.append(n)
+                    n = 0
+                lim = bend - 18 if bend > 18 else 0
+                iters = min(WAVE - n, (lim - ip + 16) // 17) if ip < lim else 0
+                while iters > 0 and frame[ip] >> 4 != 15 and frame[ip] & 15 != 15:
+                    ip += 1 + (frame[ip] >> 4) + 2
+                    n += 1
+                    iters -= 1
+                if n > FLUSH_ABOVE or (iters == 0 and ip < lim):
+                    continue
+                if stats is not None:
+                    stats.setdefault("handover", set()).add(bend - ip)
+                tok = frame[ip]
+                ip += 1
+                lit, ml = tok >> 4, tok & 15
+                if lit == 15:
+                    lit, ip = chain(lit, ip)
+                ip += lit
+                if ip == bend:
+                    n += nrec(lit, 0)
+                    break
+                ip += 2
+                if ml == 15:
+                    ml, ip = chain(ml, ip)
+                n += nrec(lit, ml + 4)
+        ip += bck
+    if n:
+        out.append(n)
+    return out
+
+
+def model_decode(frame: bytes, ulen: int, batch=WAVE, stats: dict | None = None) -> bytes:
+    """batch: records per batch, or the list of batch sizes (kernel_batches).  stats (optional)
+    counts the paths taken: "chase" same-pass chase iterations, "far" / "near" match bytes of short
+    batches read from HBM / from the ring, "long_batches", "ring_rebuilds", "wide_runs" (literal
+    runs a long batch copies 1 KiB at a time) and "split_records"."""
+    recs = parse_frame(frame, stats)
+
+    def count(key, n=1):
+        if stats is not None:
+            stats[key] = stats.get(key, 0) + int(n)
+
     out = np.full(ulen, -1, dtype=np.int64)       # HBM (what stores have produced so far)
     ring = np.full(RING, -1, dtype=np.int64)      # the wave's LDS history
     src = np.frombuffer(frame, dtype=np.uint8)
     obase = 0
-    for b0 in range(0, len(recs), batch):         # the kernel executes 59..64 records at a time
-        batch_recs = recs[b0:b0 + batch]
+    sizes = [batch] * ((len(recs) + batch - 1) // batch) if isinstance(batch, int) else list(batch)
+    assert sum(sizes) >= len(recs)
+    b0 = 0
+    for size in sizes:                            # the kernel executes 57..64 records at a time
+        batch_recs = recs[b0:b0 + size]
+        b0 += size
         lit = np.array([r[1] for r in batch_recs], dtype=np.int64)
         ml = np.array([r[2] for r in batch_recs], dtype=np.int64)
         off = np.array([r[3] for r in batch_recs], dtype=np.int64)
@@ -114,6 +215,9 @@ def model_decode(frame: bytes, ulen: int, batch: int = WAVE) -> bytes:
         mi = np.cumsum(ml)
         mtot = int(mi[-1]) if len(mi) else 0
         short = span + 4 * WAVE < RING
+        if not short:
+            count("long_batches")
+            count("wide_runs", (lit >= 512).sum())
         for t0 in range(0, mtot, WAVE):
             t = np.arange(t0, min(t0 + WAVE, mtot))
             s = np.searchsorted(mi, t, side="right")
@@ -126,9 +230,12 @@ def model_decode(frame: bytes, ulen: int, batch: int = WAVE) -> bytes:
                 pend = (j < len(d)) & (d[np.minimum(j, len(d) - 1)] == q)
                 if not pend.any():
                     break
+                count("chase")
                 q = np.where(pend, q[np.minimum(j, len(d) - 1)], q)
             if short:
                 far = oend - q >= RING
+                count("far", far.sum())
+                count("near", (~far).sum())
                 v = np.where(far, out[q], ring[q % RING])
             else:
                 v = out[q]          # long batch: HBM read-back after s_waitcnt
@@ -136,6 +243,7 @@ def model_decode(frame: bytes, ulen: int, batch: int = WAVE) -> bytes:
             out[d] = v
             ring[d % RING] = v
         if not short:               # rebuild the ring from HBM
+            count("ring_rebuilds")
             lo = max(0, oend - RING)
             ring[np.arange(lo, oend) % RING] = out[lo:oend]
         obase = oend
