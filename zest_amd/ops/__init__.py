@@ -393,7 +393,7 @@ def merkle_roots(hashes: torch.Tensor, sizes: torch.Tensor, jobs, file_hash: boo
             raise ValueError("merkle job out of range")
     if hashes.device.type != "cuda":
         hs = hashes.numpy()
-        sz = sizes.numpy()
+        sz = sizes.to(torch.int64).contiguous().numpy().view(np.uint64)  # the same 64 bits the kernel reads
         out = np.empty((nj, 32), dtype=np.uint8)
         for j, (b, n) in enumerate(jobs):
             leaves = [(hs[i].tobytes(), int(sz[i])) for i in range(b, b + n)]
