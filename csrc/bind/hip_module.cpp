@@ -94,6 +94,13 @@ PYBIND11_MODULE(_hip, m) {
     py::gil_scoped_release nogil;
     zest::gpurt::PinnedBuf::free_raw(reinterpret_cast<uint8_t*>(p), a.first, a.second);
   });
+  // The address at which kernels on the current device see pinned host memory (host_malloc'd, or a
+  // pinned torch tensor); raises when the memory is not mapped for the device.
+  m.def("host_device_pointer", [](uintptr_t p) {
+    void* d = nullptr;
+    check(hipHostGetDevicePointer(&d, reinterpret_cast<void*>(p), 0), "hipHostGetDevicePointer");
+    return reinterpret_cast<uintptr_t>(d);
+  });
   // Let the current device's copy engines read `peer`'s memory directly over xGMI (IPC exchange).
   m.def("enable_peer_access", [](int peer) {
     int dev = 0;
@@ -269,4 +276,10 @@ PYBIND11_MODULE(_hip, m) {
                          P<const uint64_t>(out_off), n, P<uint8_t>(out), S(st)),
           "zg_pack_chunks");
   });
+  m.def("serve_pack", [](uintptr_t src, uintptr_t ser_end, uint32_t n, uint64_t lo, uint64_t hi, uintptr_t out,
+                         uintptr_t st) {
+    check(zg_serve_pack(P<const uint64_t>(src), P<const uint64_t>(ser_end), n, lo, hi, P<uint8_t>(out), S(st)),
+          "zg_serve_pack");
+  }, py::arg("src_table"), py::arg("ser_end_table"), py::arg("n"), py::arg("lo"), py::arg("hi"), py::arg("out"),
+     py::arg("stream"));
 }

@@ -5,7 +5,8 @@
 //   zg_place_chunks  one wave per chunk: scheme 0 -> aligned copy, LZ4/BG4 -> LDS decode (K3)
 //   zg_hash_chunks   keyed BLAKE3 of the placed bytes -> chunk hashes (K1; lane per 1 KiB leaf)
 //   zg_merkle_files  one workgroup per file: Xet Merkle tree -> root -> file hash compare (K2)
-// plus zg_cdc_candidates (K5), zg_pack_xorbs (K7) and synthetic data generators.
+// plus zg_cdc_candidates (K5), zg_pack_xorbs (K7), zg_serve_pack (K9, seeding from decoded bytes) and
+// synthetic data generators.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -165,6 +166,15 @@ hipError_t zg_pack_frames(const uint64_t* src, const uint32_t* clen, const uint3
 // Pack uncompressed chunks into serialized xorb bodies: header (version 0, scheme 0) + payload.
 hipError_t zg_pack_chunks(const uint8_t* data, const uint64_t* data_off, const uint32_t* lens,
                           const uint64_t* out_off, int n, uint8_t* out, hipStream_t stream);
+
+// K9 (serve.hip): write bytes [lo, hi) of a resident run's scheme-0 serialized stream to
+// out[0, hi - lo).  src[i]: device address of chunk i's decoded bytes (any alignment); ser_end[i]:
+// serialized end offset of chunk i relative to the run (sum of len + 8); both tables stay on the
+// device, so a request is a launch with scalars.  out: 16-byte aligned, device or device-visible
+// pinned host memory; nothing outside out[0, hi - lo) is written.  The caller vouches for the
+// tables and for hi <= ser_end[n - 1].
+hipError_t zg_serve_pack(const uint64_t* src, const uint64_t* ser_end, uint32_t n, uint64_t lo, uint64_t hi,
+                         uint8_t* out, hipStream_t stream);
 
 // K8: pull each segment's bytes from a peer's IPC-mapped arena (xGMI) into this GPU's arena;
 // every segment is read concurrently.  src[i] and dst[i] must be congruent mod 16.

@@ -350,6 +350,48 @@ def main():
         ms = timed(lambda: ops.merkle_roots(hs, sz, jobs), a.iters)
         emit(kernel="merkle_8x80k_leaves", ms=ms, leaves=nl * 8)
 
+    if want("serve"):
+        # K9 serve_pack: a resident run of CDC-sized chunks (8-128 KiB at odd addresses) serialized in
+        # the seeder's 8 MiB pieces, into HBM and into pinned host memory (what a resident seeder
+        # does per response); next to it the serialized seeder's step, a D2H copy of the same pieces
+        m = min(n, 1 << 30)
+        rng = np.random.default_rng(5)
+        ln = rng.integers(8192, 131073, m // 65536)
+        gaps = rng.integers(0, 16, len(ln))
+        so = np.cumsum(ln + gaps) - ln
+        keep = so + ln <= m
+        ln, so = ln[keep], so[keep]
+        run = ops.ServeRun(np.uint64(arena.data_ptr()) + so.astype(np.uint64), ln, buffers=[arena])
+        piece = 8 << 20
+        wins = [(o, min(run.total, o + piece)) for o in range(0, run.total, piece)]
+        d_out = ops.padded_empty(run.total, dev)
+        host = H.host_malloc(run.total)
+
+        def serve(base, cap):
+            for lo, hi in wins:
+                ops.serve_pack(run, lo=lo, hi=hi, out=(base + lo, cap - lo))
+
+        try:
+            for name, fn in (("serve_pack[hbm]", lambda: [ops.serve_pack(run, lo=lo, hi=hi, out=d_out[lo:hi])
+                                                          for lo, hi in wins]),
+                             ("serve_pack[pinned]", lambda: serve(host, run.total)),
+                             ("d2h_memcpy_of_serialized[pinned]",
+                              lambda: [H.memcpy_async(host + lo, d_out.data_ptr() + lo, hi - lo, st) for lo, hi in wins])):
+                ms = timed(fn, a.iters)
+                emit(kernel=name, bytes=run.total, ms=ms, gbps=run.total / ms / 1e6, chunks=run.n, pieces=len(wins),
+                     piece_mib=piece >> 20)
+            # the pinned copy now holds the D2H copy of serve_pack[hbm]'s output: check it on the host
+            import ctypes
+
+            got = np.ctypeslib.as_array((ctypes.c_uint8 * run.total).from_address(host))
+            idx = C.index_chunks(got[:int(run.ser_end[7])])
+            assert [e[1] for e in idx] == [int(x) for x in ln[:8]]
+            assert got[8:8 + int(ln[0])].tobytes() == arena[int(so[0]):int(so[0] + ln[0])].cpu().numpy().tobytes()
+        finally:
+            torch.cuda.synchronize()
+            H.host_free(host)
+        del d_out
+
     if want("h2d"):
         pin = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()
         d = torch.empty(1 << 30, dtype=torch.uint8, device=dev)

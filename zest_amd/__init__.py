@@ -57,7 +57,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
          p2p: bool = True, peers=None, tracker=None, dht: bool = True, dht_bootstrap=None, include=None,
          group=None, repo_type: str = "model", verbose: bool = False, direct: bool | None = None,
          save_snapshot: bool = False, threads: int = 16, staging_bytes: int = 1 << 30, stats: dict | None = None,
-         exchange: str = "auto", round_bytes: int | None = None):
+         exchange: str = "auto", round_bytes: int | None = None, seed=False):
     """Download `repo@revision` via zest.
 
     * default: returns the HF-cache snapshot directory (reference behaviour).
@@ -79,7 +79,20 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       snapshot is written unless `save_snapshot=True`; `include` (file-name suffixes) filters the
       safetensors files.  direct=False: the reference's path -- the CLI writes the HF-cache
       snapshot, which is then loaded and (verify=True) hash-checked on the device.
+    * seed=True (or a port number), single-GPU direct pulls only: after the files verify, their xorbs
+      are seeded to BEP XET peers straight from the HBM the returned tensors occupy -- no serialized
+      copy, no disk (zest_amd.seed.ResidentSeedServer; `zest_amd.seed.active()` lists the servers,
+      `zest_amd.seed.stop_all()` / `zest_amd.stop()` stop them).  Keep the tensors read-only meanwhile.
     """
+    if seed is not False and seed is not None:
+        if device == "all":
+            raise ValueError("seed= is not supported with device='all' (swarm pulls): use a single device='cuda:N'")
+        if device is None and not as_tensors:
+            raise ValueError("seed= needs a device pull (device='cuda:N'); snapshot pulls are seeded by the "
+                             "background server")
+        if direct is False:
+            raise ValueError("seed= is not supported with direct=False (the snapshot path): it serves the "
+                             "buffers of a device-direct pull")
     _init()
     kw = dict(p2p=p2p, peers=peers, tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap, include=include,
               verify=verify, repo_type=repo_type, verbose=verbose)
@@ -99,7 +112,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
 
         return pull_to_device(repo, revision, device or "cuda:0", p2p=p2p, peers=peers, tracker=tracker, dht=dht,
                               dht_bootstrap=dht_bootstrap, repo_type=repo_type, save_snapshot=save_snapshot,
-                              threads=threads, staging_bytes=staging_bytes, include=include)
+                              threads=threads, staging_bytes=staging_bytes, include=include, seed=seed)
     from .device import load_snapshot
 
     res = _client.pull_detailed(repo, revision, **kw)
@@ -121,7 +134,12 @@ def status() -> dict:
 
 
 def stop() -> None:
-    """Stop the background server."""
+    """Stop the background server and every resident seed server started by pull(..., seed=...)."""
+    import sys
+
+    zseed = sys.modules.get(__name__ + ".seed")
+    if zseed is not None:
+        zseed.stop_all()
     _init()
     _server.stop()
 

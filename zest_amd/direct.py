@@ -10,6 +10,13 @@ device="cpu": the same fetch through the host waterfall straight into CPU tensor
 Non-Xet files of the repo (config, tokenizer, small safetensors) are fetched by the native host
 pull (`include=` filter) and loaded like the disk path.  With `save_snapshot=True` the verified
 device bytes are also written to the HF cache snapshot so later `from_pretrained` calls hit disk.
+
+    tensors = pull_to_device("meta-llama/Llama-3.1-8B", device="cuda:0", seed=True)
+
+`seed=True` (or a port number): once the files have verified, their xorbs are served to BEP XET
+peers straight from the HBM the returned tensors live in (`zest_amd.seed.ResidentSeedServer`): no
+serialized second copy, no disk.  The server is kept in `zest_amd.seed.active()` until
+`zest_amd.seed.stop_all()`.  Treat the tensors as read-only while seeding.
 """
 from __future__ import annotations
 
@@ -24,10 +31,17 @@ from . import device as zdev
 
 def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: bool = True, peers=None,
                    tracker=None, dht: bool = True, dht_bootstrap=None, repo_type: str = "model",
-                   save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None):
+                   save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False):
     dev = torch.device(device)
     if dev.type not in ("cuda", "cpu"):
         raise ValueError("pull_to_device needs a GPU or the CPU")
+    seed_port = None
+    if seed is not False and seed is not None:
+        from .seed import seed_port as _seed_port
+
+        seed_port = _seed_port(seed)
+        if dev.type != "cuda":
+            raise ValueError(f"seed= serves weights resident in GPU memory: unsupported with device={str(device)!r}")
     commit, files = _core.list_repo_files(repo, revision, repo_type)
     if include:  # file-name suffixes, as `zest pull --include` (csrc/core/pull.cpp)
         files = [f for f in files if any(f["path"].endswith(x) for x in include)]
@@ -50,7 +64,13 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
         bufs = [ops.padded_empty(f["size"], dev)[:f["size"]] for f in xet]
         torch.cuda.synchronize(dev)  # allocations visible to the pull's private stream
         # one pipeline for all files: staging batches cross file boundaries
-        dp.pull_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
+        stats = dp.pull_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
+        if seed_port is not None:  # the files verified: serve their xorbs from where they now live
+            from . import seed as zseed
+
+            zseed._active.append(zseed.ResidentSeedServer(
+                [(b, st["chunk_lens"], dp.term_keys(f["xet_hash"])) for f, b, st in zip(xet, bufs, stats)],
+                dev, seed_port))
         for f, buf in zip(xet, bufs):
             _add_views(out, buf, f["path"])
             if save_snapshot:

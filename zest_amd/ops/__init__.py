@@ -6,7 +6,7 @@ bad descriptor can never become an out-of-bounds GPU access.  GPU tensors always
 CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/CPU tests use.
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
-K5 cdc_candidates, K7 pack_chunks.
+K5 cdc_candidates, K7 pack_chunks, K9 serve_pack.
 """
 from __future__ import annotations
 
@@ -504,6 +504,118 @@ def pack_chunks(data: torch.Tensor, data_off: np.ndarray, lens: np.ndarray, out_
     o_off = torch.from_numpy(out_off.view(np.int64).copy()).to(dev)
     H.pack_chunks(data.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), o_off.data_ptr(), n, out.data_ptr(),
                   _stream(dev))
+
+
+# ----------------------------------------------------------------------------------------------
+# K9: serve a byte window of a resident run (decoded chunks at scattered device addresses)
+# ----------------------------------------------------------------------------------------------
+class ServeRun:
+    """A validated resident run: chunk i's decoded bytes sit at address src_addrs[i] (lens[i] bytes)
+    inside one of `buffers` (tensors that vouch for the memory; every chunk is checked against them
+    before anything is launched).  On a GPU the two tables the kernel reads (addresses, serialized
+    ends) are uploaded once and reused by every serve_pack call on the run."""
+
+    def __init__(self, src_addrs, lens, device=None, buffers=()):
+        self.src = np.ascontiguousarray(src_addrs, dtype=np.uint64)
+        lens64 = np.ascontiguousarray(lens).astype(np.uint64)
+        if self.src.ndim != 1 or lens64.shape != self.src.shape or len(self.src) == 0:
+            raise ValueError("serve_pack: src_addrs and lens must be equally long, non-empty 1-D arrays")
+        if np.any(lens64 >= (1 << 24)):
+            raise ValueError("chunk too large for a u24 header")
+        buffers = list(buffers)
+        if device is None and not buffers:
+            raise ValueError("serve_pack: give the device or the buffers the chunks live in")
+        self.device = torch.device(device) if device is not None else buffers[0].device
+        ok = lens64 == 0
+        for t in buffers:
+            if t.device != self.device:
+                raise ValueError("serve_pack: buffer on another device")
+            b0 = np.uint64(t.data_ptr())
+            b1 = np.uint64(t.data_ptr() + t.numel() * t.element_size())
+            ok |= (self.src >= b0) & (self.src <= b1) & (lens64 <= b1 - np.minimum(self.src, b1))
+        if not ok.all():
+            raise ValueError("serve_pack: chunk outside every buffer")
+        self.lens = lens64
+        self.n = len(self.src)
+        self.ser_end = np.cumsum(lens64 + np.uint64(8), dtype=np.uint64)
+        self.total = int(self.ser_end[-1])
+        self.buffers = buffers  # keeps the chunk memory alive
+        self.tab = None
+        if self.device.type == "cuda":
+            tab = np.concatenate([self.src, self.ser_end]).view(np.int64)
+            self.tab = torch.from_numpy(tab.copy()).to(self.device)
+
+
+def serve_pack(src_addrs, lens=None, lo: int = 0, hi: int | None = None, out=None, device=None, buffers=()):
+    """Bytes [lo, hi) of the scheme-0 serialized stream (per chunk: 8-byte header + payload) of a
+    resident run, written by the K9 kernel (csrc/gpu/serve.hip) from the chunks' decoded bytes.
+
+    src_addrs: chunk addresses (or a ServeRun, which skips validation and the table upload); lens:
+    chunk lengths; buffers: the tensors holding the chunks.  out: None (a new device tensor), a
+    uint8 tensor on the run's device or in pinned host memory, or (address, nbytes) of
+    device-visible memory (ops.hip().host_malloc); 16-byte aligned.  Returns out[:hi - lo] (None for
+    a raw address); the launch is asynchronous on the current stream.  CPU runs (host addresses)
+    take a NumPy path that produces the same bytes."""
+    run = src_addrs if isinstance(src_addrs, ServeRun) else ServeRun(src_addrs, lens, device, buffers)
+    lo = int(lo)
+    hi = run.total if hi is None else int(hi)
+    if not 0 <= lo <= hi <= run.total:
+        raise ValueError("serve_pack: window outside the run's serialized stream")
+    n = hi - lo
+    if run.device.type != "cuda":
+        got = torch.from_numpy(_serve_pack_cpu(run, lo, hi))
+        if out is None:
+            return got
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.numel() < n:
+            raise ValueError("serve_pack: out must be a uint8 tensor of at least hi - lo bytes")
+        out.reshape(-1)[:n].copy_(got)
+        return out.reshape(-1)[:n]
+    res = None
+    if out is None:
+        res = torch.empty(max(n, 1), dtype=torch.uint8, device=run.device)[:n]
+        ptr = res.data_ptr()
+    elif isinstance(out, torch.Tensor):
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < n:
+            raise ValueError("serve_pack: out must be a contiguous uint8 tensor of at least hi - lo bytes")
+        if out.device != run.device and not (out.device.type == "cpu" and out.is_pinned()):
+            raise ValueError("serve_pack: out must be on the run's device or in pinned host memory")
+        res = out.reshape(-1)[:n]
+        ptr = out.data_ptr()
+        host = out.device.type == "cpu"
+    else:
+        ptr, cap = int(out[0]), int(out[1])
+        host = True  # a raw address is pinned host memory: ask HIP where the device sees it
+        if cap < n:
+            raise ValueError("serve_pack: out too small")
+    if n == 0:
+        return res
+    if out is not None and host:
+        ptr = hip().host_device_pointer(ptr)
+    if ptr & 15:
+        raise ValueError("serve_pack: out must be 16-byte aligned")
+    hip().serve_pack(run.tab.data_ptr(), run.tab.data_ptr() + 8 * run.n, run.n, lo, hi, ptr, _stream(run.device))
+    return res
+
+
+def _serve_pack_cpu(run: ServeRun, lo: int, hi: int) -> np.ndarray:
+    import ctypes
+
+    out = np.empty(hi - lo, dtype=np.uint8)
+    c = int(np.searchsorted(run.ser_end, lo, side="right"))  # first chunk ending after lo
+    while c < run.n:
+        e = int(run.ser_end[c])
+        ln = int(run.lens[c])
+        s = e - ln - 8
+        if s >= hi:
+            break
+        ser = np.empty(ln + 8, dtype=np.uint8)
+        ser[:8] = np.frombuffer(bytes([0]) + ln.to_bytes(3, "little") + bytes([0]) + ln.to_bytes(3, "little"), np.uint8)
+        if ln:
+            ser[8:] = np.frombuffer(ctypes.string_at(int(run.src[c]), ln), dtype=np.uint8)
+        a, b = max(lo, s), min(hi, e)
+        out[a - lo:b - lo] = ser[a - s:b - s]
+        c += 1
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
