@@ -1,7 +1,7 @@
 // K7b: Xet chunk compression on MI355X (gfx950): BG4 byte grouping + LZ4 frame, one wave per chunk.
 // SURVEY §2.G K7 ("xorb assembly, optionally compress").  Output frames use the same layout as the
 // host encoder (csrc/core/lz4.cpp::compress_frame: FLG 0x60, one independent block, no checksums), so
-// the host decoder, hf_xet and k_decode_lz4 all read them.
+// the host decoder, hf_xet and the GPU decoders (lz4seq.hip) all read them.
 //
 // Match finding is window-parallel: the 64 lanes look up positions ip .. ip+63 at once in a per-wave
 // LDS hash table of (position, 4-byte value) entries — the stored value replaces a reload of the

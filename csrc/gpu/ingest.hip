@@ -3,14 +3,10 @@
 // ingest).  Host oracle: csrc/core/{xorb,lz4,blake3}.cpp.
 //
 // Buffers handed to these kernels must be padded by >= 4 KiB past their logical end: the
-// alignment-fixing loads read whole aligned dwords (and the LZ4 window reads 256-byte lines).
+// alignment-fixing loads read whole aligned dwords (and the LZ4 parse reads 8 bytes at a time).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-
 #include "blake3_dev.h"
-#include "lz4win.h"
 #include "wave64.h"
 #include "zgpu.h"
 
@@ -18,13 +14,9 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
-constexpr uint32_t kMaxChunk = 128u * 1024u;  // Xet CDC maximum chunk size
-
-__device__ __forceinline__ void report(unsigned long long* err, uint32_t code, uint32_t idx) {
-  if (err) atomicCAS(err, 0ull, (static_cast<unsigned long long>(code) << 32) | idx);
-}
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
+using zwv::kMaxChunk;
+using zwv::lane_id;
+using zwv::report;
 
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -363,377 +355,6 @@ __global__ void __launch_bounds__(256) k_place_raw(const uint8_t* __restrict__ s
 }
 
 // --------------------------------------------------------------------------------------------
-// K3b: LZ4-frame (+BG4) decode.  One wave per chunk, 4 waves per 256-thread block, persistent
-// grid.  Decoded bytes go through a small per-wave LDS history ring (4 KiB by default, so 8 waves
-// per SIMD stay resident) and are flushed to HBM in 16-byte stores every 2 KiB.
-//
-//  * compressed stream: a 512-byte window held as two dwords per lane; token / length bytes are
-//    read with v_readlane (uniform), literal bytes lane-parallel with ds_bpermute; the window
-//    slides by 256 bytes so the next line's load overlaps the current line's parsing.
-//  * lz4_fast takes the common short sequence (no length-extension bytes) with every check folded
-//    into loop bounds and unconditional ring writes; the general path handles the rest.
-//  * match copies: lane i of a 64-byte block reads source o - off*(1 + i/off) (the periodic form
-//    of an overlapping copy, always a final byte); distances <= ring - 320 come from the LDS ring,
-//    longer ones from HBM with L2-coherent loads (sc1, agent scope) after s_waitcnt vmcnt(0) --
-//    those bytes were flushed by this wave at least ring - 320 - 2 KiB earlier.
-//  * BG4: the grouped stream is scattered to its interleaved position (4*j + g) on flush, and
-//    long-distance match reads use the same mapping, so no regroup pass or scratch is needed.
-//  * chunks clipped by [clip_lo, clip_hi) decode into a 128 KiB slot of the caller's per-launch
-//    scratch (one for the chunk straddling clip_lo, one for clip_hi), then the clipped range is
-//    copied out.  The scratch belongs to the launch, so clipped decodes on several streams never
-//    share it.
-// --------------------------------------------------------------------------------------------
-// Ring geometry (bytes per wave) is a template parameter RB: a larger ring keeps more match
-// sources in LDS (fewer L2 read-backs) at the price of fewer resident waves per CU.
-template <uint32_t RB> struct RingGeo {
-  static constexpr uint32_t kMask = RB - 1;
-  static constexpr uint32_t kReach = RB - 256 - 64;  // max match distance served from the ring
-};
-constexpr uint32_t kFlushAt = 2048;
-
-constexpr uint32_t kClipSlot = kMaxChunk + 256;
-static_assert(2 * kClipSlot == ZG_CLIP_SCRATCH_BYTES, "clip scratch layout");
-
-using zgw::Win;
-using zgw::load_u8_coherent;
-using zgw::win_init;
-using zgw::win_lane_u8;
-using zgw::win_seek;
-using zgw::win_u8;
-
-// Optional decode profile (ZG_LZ4_PROF=1 selects the kProf instantiation).
-__device__ unsigned long long g_lz4_prof[10];
-__device__ __forceinline__ uint64_t clk() { return __builtin_amdgcn_s_memtime(); }
-
-struct Sink {
-  uint8_t* ring;  // this wave's LDS ring (16-byte aligned)
-  uint8_t* out;   // chunk byte 0 in HBM (dst or scratch)
-  uint32_t tmod;  // ring index of stream byte p = (tmod + p) & kRingMask
-  uint32_t n;     // expected decoded size
-  uint32_t op;    // bytes produced
-  uint32_t fp;    // bytes flushed
-  uint32_t g1, g2, g3;
-  bool bg4;
-  // profile counters (kProf only)
-  uint64_t t_lit, t_match, t_flush, nseq, lit_bytes, match_bytes, nfar, nflush, nshort;
-};
-
-// Grouped-stream position -> byte offset in the chunk (identity unless BG4).
-__device__ __forceinline__ uint32_t out_pos(const Sink& s, uint32_t p) {
-  if (!s.bg4) return p;
-  const uint32_t a1 = p >= s.g1, a2 = p >= s.g2, a3 = p >= s.g3;
-  uint32_t base = 0;  // selects, not branches: the lanes of one flush straddle group boundaries
-  base = a1 ? s.g1 : base;
-  base = a2 ? s.g2 : base;
-  base = a3 ? s.g3 : base;
-  return 4 * (p - base) + a1 + a2 + a3;
-}
-
-template <uint32_t RB>
-__device__ void sink_flush(Sink& s, uint32_t upto, bool final, uint32_t lane) {
-  __builtin_amdgcn_wave_barrier();
-  if (s.bg4) {
-    for (uint32_t i = s.fp + lane; i < upto; i += kWave) s.out[out_pos(s, i)] = s.ring[(s.tmod + i) & RingGeo<RB>::kMask];
-    s.fp = upto;
-    return;
-  }
-  uint32_t p = s.fp;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(s.out) + p;
-  uint32_t head = uint32_t((16 - (a & 15)) & 15);
-  if (head > upto - p) head = upto - p;
-  if (lane < head) s.out[p + lane] = s.ring[(s.tmod + p + lane) & RingGeo<RB>::kMask];
-  p += head;
-  const uint32_t nvec = (upto - p) >> 4;
-  for (uint32_t v = lane; v < nvec; v += kWave) {
-    const uint32_t q = p + 16 * v;
-    const uint4 x = *reinterpret_cast<const uint4*>(s.ring + ((s.tmod + q) & RingGeo<RB>::kMask));
-    *reinterpret_cast<uint4*>(s.out + q) = x;
-  }
-  p += 16 * nvec;
-  if (final) {
-    if (lane < upto - p) s.out[p + lane] = s.ring[(s.tmod + p + lane) & RingGeo<RB>::kMask];
-    p = upto;
-  }
-  s.fp = p;
-}
-
-template <bool kProf, uint32_t RB>
-__device__ __forceinline__ void sink_advance(Sink& s, uint32_t cnt, uint32_t lane) {
-  s.op += cnt;
-  if (s.op - s.fp >= kFlushAt) {
-    const uint64_t t0 = kProf ? clk() : 0;
-    sink_flush<RB>(s, s.op, false, lane);
-    if (kProf) {
-      s.t_flush += clk() - t0;
-      s.nflush++;
-    }
-  }
-}
-
-// Copy `len` literal bytes starting at stream position a.
-template <bool kProf, uint32_t RB>
-__device__ __forceinline__ void copy_literals(Sink& s, Win& w, uint32_t a, uint32_t len, uint32_t lane) {
-  for (uint32_t b = 0; b < len; b += kWave) {
-    const uint32_t cnt = len - b < kWave ? len - b : kWave;
-    win_seek(w, a + b, lane);
-    const uint32_t v = win_lane_u8(w, a + b, lane);
-    // unconditional: lanes past the literal write ring slots ahead of op (see lz4_fast)
-    s.ring[(s.tmod + s.op + lane) & RingGeo<RB>::kMask] = uint8_t(v);
-    sink_advance<kProf, RB>(s, cnt, lane);
-  }
-}
-
-template <bool kProf, uint32_t RB>
-__device__ __forceinline__ void copy_match(Sink& s, uint32_t off, uint32_t ml, uint32_t lane) {
-  // lane i of each 64-byte block copies from distance back = off * (1 + i / off): the periodic form
-  // of an overlapping copy, so every source byte is already final.
-  uint32_t back = off;
-  if (off < kWave) {
-    const uint32_t magic = (65536u + off - 1) / off;  // exact floor(lane / off) for lane, off < 64
-    back = off * (1 + ((lane * magic) >> 16));
-  }
-  if (off <= RingGeo<RB>::kReach) {
-    for (uint32_t b = 0; b < ml; b += kWave) {
-      const uint32_t cnt = ml - b < kWave ? ml - b : kWave;
-      const uint32_t o = s.op + lane;
-      __builtin_amdgcn_wave_barrier();
-      if (lane < cnt) s.ring[(s.tmod + o) & RingGeo<RB>::kMask] = s.ring[(s.tmod + o - back) & RingGeo<RB>::kMask];
-      sink_advance<kProf, RB>(s, cnt, lane);
-    }
-  } else {
-    for (uint32_t b = 0; b < ml; b += kWave) {
-      const uint32_t cnt = ml - b < kWave ? ml - b : kWave;
-      const uint32_t o = s.op + lane;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane < cnt) s.ring[(s.tmod + o) & RingGeo<RB>::kMask] = uint8_t(load_u8_coherent(s.out + out_pos(s, o - back)));
-      sink_advance<kProf, RB>(s, cnt, lane);
-    }
-  }
-}
-
-// Fast path for the common sequence shape of weight data: lit < 15 and ml < 19 (no length-
-// extension bytes), a match source inside the LDS ring, >= 18 stream bytes left in the block.
-// Measured (rocprofv3 PMC, BG4 bf16): the general path below is SALU-issue bound -- ~107 scalar
-// instructions per sequence against one scalar unit per CU shared by ~20 waves -- so here every
-// check is folded into two loop bounds (ip_lim: block end / stream window; op_lim: output room /
-// next flush) and one offset range test, bytes come from one window gather (lane l = stream byte
-// ip + l) plus read-lanes, and ring writes are unconditional: lanes past the sequence write into
-// ring slots ahead of `op`, which are rewritten before they are flushed and lie more than
-// RingGeo<RB>::kReach behind every later match source.  Returns at the first sequence it cannot take.
-template <bool kProf, uint32_t RB>
-__device__ __forceinline__ void lz4_fast(Sink& s, Win& w, uint32_t& ip, uint32_t end, uint32_t lane) {
-  const uint32_t ip_end = end >= 18 ? end - 18 : 0;
-  const uint32_t op_room = s.n >= 32 ? s.n - 32 : 0;
-  while (true) {
-    win_seek(w, ip, lane);
-    const uint32_t ip_lim = ip_end < w.wofs + 256 ? ip_end : w.wofs + 256;
-    if (ip >= ip_lim) return;
-    uint32_t op_lim = op_room < s.fp + kFlushAt ? op_room : s.fp + kFlushAt;
-    // One gather per sequence, aligned to its literals: lane l holds stream byte ip + 1 + l, so the
-    // offset (lanes lit, lit + 1) and the NEXT token (lane lit + 2) are read-lanes of the same vector.
-    uint32_t token = win_u8(w, ip);
-    do {
-      if (s.op >= op_lim) {
-        if (s.op >= op_room) return;
-        sink_flush<RB>(s, s.op, false, lane);
-        op_lim = op_room < s.fp + kFlushAt ? op_room : s.fp + kFlushAt;
-      }
-      const uint32_t lit = token >> 4, mlc = token & 15;
-      const uint32_t v = win_lane_u8(w, ip + 1, lane);
-      const uint32_t off = __builtin_amdgcn_readlane(v, int(lit)) | (__builtin_amdgcn_readlane(v, int(lit + 1)) << 8);
-      const uint32_t next = __builtin_amdgcn_readlane(v, int(lit + 2));
-      // one exit test: a length-extension nibble, or an offset of 0 / before the chunk start (the
-      // general path then decodes the sequence, or reports it)
-      if (uint32_t(lit == 15) | uint32_t(mlc == 15) | uint32_t(off - 1 >= s.op + lit)) return;
-      s.ring[(s.tmod + s.op + lane) & RingGeo<RB>::kMask] = uint8_t(v);
-      const uint32_t mo = s.op + lit;
-      uint8_t m;
-      if (off <= RingGeo<RB>::kReach) {
-        uint32_t back = off;
-        if (off < kWave) back = off * (1 + ((lane * ((65536u + off - 1) / off)) >> 16));
-        __builtin_amdgcn_wave_barrier();
-        m = s.ring[(s.tmod + mo + lane - back) & RingGeo<RB>::kMask];
-      } else {
-        // Far match (off > ring reach >= 64, so no overlap): the source was flushed at least
-        // reach - kFlushAt bytes ago; wait for this wave's stores, then read it back through L2.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        m = uint8_t(load_u8_coherent(s.out + out_pos(s, mo + lane - off)));
-        if (kProf) s.nfar++;
-      }
-      __builtin_amdgcn_wave_barrier();
-      s.ring[(s.tmod + mo + lane) & RingGeo<RB>::kMask] = m;
-      __builtin_amdgcn_wave_barrier();
-      if (kProf) {
-        s.nseq++;
-        s.lit_bytes += lit;
-        s.match_bytes += mlc + 4;
-        s.nshort += off < kWave;
-      }
-      s.op = mo + mlc + 4;
-      ip += lit + 3;
-      token = next;
-    } while (ip < ip_lim);
-  }
-}
-
-// One LZ4 block at stream positions [blk, blk + blen). Returns false on malformed input.
-template <bool kProf, uint32_t RB>
-__device__ bool lz4_block(Sink& s, Win& w, uint32_t blk, uint32_t blen, uint32_t lane) {
-  const uint32_t end = blk + blen;
-  uint32_t ip = blk;
-  while (true) {
-    if (ip >= end) return false;
-    lz4_fast<kProf, RB>(s, w, ip, end, lane);
-    win_seek(w, ip, lane);
-    const uint32_t token = win_u8(w, ip);
-    ++ip;
-    uint32_t lit = token >> 4;
-    if (lit == 15) {
-      uint32_t b;
-      do {
-        if (ip >= end) return false;
-        win_seek(w, ip, lane);
-        b = win_u8(w, ip);
-        ++ip;
-        lit += b;
-      } while (b == 255);
-    }
-    if (lit > end - ip || lit > s.n - s.op) return false;
-    if (kProf) s.nseq++;
-    if (lit) {
-      const uint64_t t0 = kProf ? clk() : 0;
-      copy_literals<kProf, RB>(s, w, ip, lit, lane);
-      if (kProf) {
-        s.t_lit += clk() - t0;
-        s.lit_bytes += lit;
-      }
-    }
-    ip += lit;
-    if (ip == end) return true;  // last sequence: literals only
-    if (end - ip < 2) return false;
-    win_seek(w, ip, lane);
-    const uint32_t off = win_u8(w, ip) | (win_u8(w, ip + 1) << 8);
-    ip += 2;
-    if (off == 0 || off > s.op) return false;
-    uint32_t ml = token & 15;
-    if (ml == 15) {
-      uint32_t b;
-      do {
-        if (ip >= end) return false;
-        win_seek(w, ip, lane);
-        b = win_u8(w, ip);
-        ++ip;
-        ml += b;
-      } while (b == 255);
-    }
-    ml += 4;
-    if (ml > s.n - s.op) return false;
-    const uint64_t t0 = kProf ? clk() : 0;
-    copy_match<kProf, RB>(s, off, ml, lane);
-    if (kProf) {
-      s.t_match += clk() - t0;
-      s.match_bytes += ml;
-      s.nfar += off > RingGeo<RB>::kReach;
-      s.nshort += off < kWave;
-    }
-  }
-}
-
-// Decode an LZ4 frame of clen bytes; returns false on malformed input.
-template <bool kProf, uint32_t RB>
-__device__ bool lz4_frame(Sink& s, const uint8_t* payload, uint32_t clen, uint32_t lane) {
-  Win w;
-  win_init(w, payload, lane);
-  const uint32_t k = uint32_t(reinterpret_cast<uintptr_t>(payload) & 3);  // stream pos = k + byte index
-  if (clen < 7) return false;
-  const uint32_t magic = win_u8(w, k) | (win_u8(w, k + 1) << 8) | (win_u8(w, k + 2) << 16) | (win_u8(w, k + 3) << 24);
-  if (magic != 0x184D2204u) return false;
-  const uint32_t flg = win_u8(w, k + 4);
-  if ((flg >> 6) != 1) return false;
-  uint32_t ip = 7 + ((flg & 8) ? 8 : 0) + ((flg & 1) ? 4 : 0);
-  const bool block_ck = flg & 0x10;
-  while (true) {
-    if (ip > clen || clen - ip < 4) return false;
-    win_seek(w, k + ip, lane);
-    const uint32_t bs = win_u8(w, k + ip) | (win_u8(w, k + ip + 1) << 8) | (win_u8(w, k + ip + 2) << 16) |
-                        (win_u8(w, k + ip + 3) << 24);
-    ip += 4;
-    if (bs == 0) return true;
-    const uint32_t len = bs & 0x7FFFFFFFu;
-    if (len > clen - ip) return false;
-    if (bs & 0x80000000u) {
-      if (len > s.n - s.op) return false;
-      copy_literals<kProf, RB>(s, w, k + ip, len, lane);
-    } else if (!lz4_block<kProf, RB>(s, w, k + ip, len, lane)) {
-      return false;
-    }
-    ip += len + (block_ck ? 4 : 0);
-  }
-}
-
-template <bool kProf, uint32_t RB>
-__global__ void __launch_bounds__(256, RB <= 4096 ? 8 : 5) k_decode_lz4(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                    const ZgChunk* __restrict__ chunks, int n_chunks,
-                                                    uint64_t clip_lo, uint64_t clip_hi, uint8_t* __restrict__ clip_scratch,
-                                                    unsigned long long* err, uint64_t src_n, uint64_t dst_n) {
-  __shared__ __attribute__((aligned(16))) uint8_t rings[kWavesPerBlock][RB];
-  const uint32_t lane = lane_id();
-  const int wave = wave_uniform(int(threadIdx.x >> 6));
-  const int stride = int(gridDim.x) * kWavesPerBlock;
-  uint64_t prof[10] = {};
-  for (int c = wave_uniform(int(blockIdx.x) * kWavesPerBlock + wave); c < n_chunks; c += stride) {
-    const ZgChunk ch = chunks[c];
-    if (ch.scheme == 0) continue;
-    if (ch.src + ch.clen > src_n || ch.dst + ch.ulen > dst_n) {
-      if (lane == 0) report(err, ZG_ERR_RANGE, uint32_t(c));
-      continue;
-    }
-    if (ch.ulen > kMaxChunk) {
-      if (lane == 0) report(err, ZG_ERR_CAPACITY, uint32_t(c));
-      continue;
-    }
-    const uint64_t end = ch.dst + ch.ulen;
-    const uint64_t lo = ch.dst > clip_lo ? ch.dst : clip_lo;
-    const uint64_t hi = end < clip_hi ? end : clip_hi;
-    if (lo >= hi) continue;
-    const bool clipped = lo != ch.dst || hi != end;
-    const uint64_t t_start = kProf ? clk() : 0;
-    Sink s{};
-    s.ring = rings[wave];
-    s.out = clipped ? clip_scratch + (ch.dst < clip_lo ? 0u : kClipSlot) : dst + ch.dst;
-    s.bg4 = ch.scheme == 2;
-    s.tmod = s.bg4 ? 0u : uint32_t(reinterpret_cast<uintptr_t>(s.out) & RingGeo<RB>::kMask);
-    s.n = ch.ulen;
-    const uint32_t q = ch.ulen >> 2, r = ch.ulen & 3;
-    s.g1 = q + (r > 0 ? 1u : 0u);
-    s.g2 = s.g1 + q + (r > 1 ? 1u : 0u);
-    s.g3 = s.g2 + q + (r > 2 ? 1u : 0u);
-    const bool ok = lz4_frame<kProf, RB>(s, src + ch.src, ch.clen, lane);
-    if (!ok) {
-      if (lane == 0) report(err, ZG_ERR_LZ4, uint32_t(c));
-      continue;
-    }
-    if (s.op != ch.ulen) {
-      if (lane == 0) report(err, ZG_ERR_SIZE, uint32_t(c));
-      continue;
-    }
-    sink_flush<RB>(s, s.op, true, lane);
-    if (kProf) {
-      const uint64_t v[10] = {s.t_lit, s.t_match, s.t_flush, clk() - t_start, s.nseq,
-                              s.lit_bytes, s.match_bytes, s.nfar, s.nflush, s.nshort};
-      for (int i = 0; i < 10; ++i) prof[i] += v[i];
-    }
-    if (clipped) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const uint32_t a = uint32_t(lo - ch.dst), len = uint32_t(hi - lo);
-      for (uint32_t i = lane; i < len; i += kWave) dst[lo + i] = uint8_t(load_u8_coherent(s.out + a + i));
-    }
-  }
-  if (kProf && lane == 0)
-    for (int i = 0; i < 10; ++i) atomicAdd(&g_lz4_prof[i], (unsigned long long)prof[i]);
-}
-
-// --------------------------------------------------------------------------------------------
 // K1: keyed BLAKE3 chunk hashes, latency path (launches without scratch; the leaf-flat pipeline
 // in blake3_flat.hip is the throughput path).  One wave per Xet chunk (4 per 256-thread block);
 // lane l owns BLAKE3 chunks l, l+64 (<= 128 for a 128 KiB Xet chunk); chaining values are merged
@@ -837,63 +458,8 @@ hipError_t zg_place_chunks(const uint8_t* src, uint64_t src_n, uint8_t* dst, uin
                      dst, chunks, n_chunks, clip_lo, clip_hi, src_n, dst_n);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // ZG_LZ4_SEQ=0 forces the LDS-ring decoder (A/B runs); clip windows always use it.
-  static const bool batched = [] {
-    const char* v = getenv("ZG_LZ4_SEQ");
-    return !(v && *v == '0');
-  }();
-  if (batched && !clipped) return zg_lz4_batched_decode(src, src_n, dst, dst_n, chunks, n_chunks, err, stream);
-  const int blocks = (n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-  // ZG_LZ4_GRID caps the persistent grid (occupancy experiments: 256 = one wave per SIMD).
-  static const int grid_cap = [] {
-    const char* v = getenv("ZG_LZ4_GRID");
-    const int g = v ? atoi(v) : 0;
-    return g > 0 && g < 1280 ? g : 1280;
-  }();
-  static const bool prof = [] {
-    const char* v = getenv("ZG_LZ4_PROF");
-    return v && *v && *v != '0';
-  }();
-  // ZG_LZ4_RING = ring KiB per wave (4, 8, 16 or 32); resident blocks per CU follow from the LDS.
-  // Measured on BG4 bf16 (1 GiB, 16.7k chunks): 4 KiB 46.3 GB/s (8 waves/SIMD, more matches read
-  // back from L2), 8 KiB 38.2, 16 KiB 29.9, 32 KiB 18.5 -- occupancy beats ring reach.
-  static const int ring_kib = [] {
-    const char* v = getenv("ZG_LZ4_RING");
-    const int k = v ? atoi(v) : 4;
-    return k == 8 || k == 16 || k == 32 ? k : 4;
-  }();
-  const int per_cu = ring_kib == 4 ? 8 : ring_kib == 8 ? 5 : ring_kib == 16 ? 2 : 1;
-  const int cap = grid_cap < 256 * per_cu ? grid_cap : 256 * per_cu;
-  const int grid = blocks < cap ? blocks : cap;
-  if (prof) {
-    unsigned long long zero[10] = {};
-    hipMemcpyToSymbolAsync(HIP_SYMBOL(g_lz4_prof), zero, sizeof zero, 0, hipMemcpyHostToDevice, stream);
-  }
-#define ZG_LZ4_LAUNCH(P, R)                                                                                       \
-  hipLaunchKernelGGL((k_decode_lz4<P, R>), dim3(grid), dim3(256), 0, stream, src, dst, chunks, n_chunks, clip_lo, \
-                     clip_hi, clip_scratch, err, src_n, dst_n)
-  if (ring_kib == 4) {
-    if (prof) ZG_LZ4_LAUNCH(true, 4096); else ZG_LZ4_LAUNCH(false, 4096);
-  } else if (ring_kib == 16) {
-    if (prof) ZG_LZ4_LAUNCH(true, 16384); else ZG_LZ4_LAUNCH(false, 16384);
-  } else if (ring_kib == 32) {
-    if (prof) ZG_LZ4_LAUNCH(true, 32768); else ZG_LZ4_LAUNCH(false, 32768);
-  } else {
-    if (prof) ZG_LZ4_LAUNCH(true, 8192); else ZG_LZ4_LAUNCH(false, 8192);
-  }
-#undef ZG_LZ4_LAUNCH
-  if (prof) {
-    unsigned long long v[10];
-    hipMemcpyFromSymbolAsync(v, HIP_SYMBOL(g_lz4_prof), sizeof v, 0, hipMemcpyDeviceToHost, stream);
-    hipStreamSynchronize(stream);
-    if (v[4])
-      fprintf(stderr,
-              "{\"lz4_prof\": {\"chunks\": %d, \"t_lit\": %llu, \"t_match\": %llu, \"t_flush\": %llu, \"t_total\": %llu, "
-              "\"nseq\": %llu, \"lit_bytes\": %llu, \"match_bytes\": %llu, \"nfar\": %llu, \"nflush\": %llu, "
-              "\"nshort\": %llu}}\n",
-              n_chunks, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
-  }
-  return hipGetLastError();
+  if (!clipped) return zg_lz4_batched_decode(src, src_n, dst, dst_n, chunks, n_chunks, err, stream);
+  return zg_lz4_decode_clipped(src, src_n, dst, dst_n, chunks, n_chunks, clip_lo, clip_hi, clip_scratch, err, stream);
 }
 
 hipError_t zg_hash_chunks(const uint8_t* dst, uint64_t dst_n, const ZgChunk* chunks, int n_chunks, uint8_t* hashes,

@@ -1,11 +1,11 @@
 // K3c: batched LZ4 / BG4-LZ4 decode for gfx950 (CDNA4, wave64).
 //
 // Xet weight chunks decode into ~6.8k LZ4 sequences per 64 KiB (BG4 bf16: the exponent planes
-// are almost all 4-5 byte matches).  The LDS-ring decoder (k_decode_lz4, ingest.hip) executes
-// those sequences one at a time with the whole wave, so ~5 of 64 lanes do useful work and every
-// sequence pays a chain of read-lanes, LDS round trips and barriers (PMC: ~450 SIMD cycles per
-// sequence).  This decoder keeps one wave per chunk (full occupancy) but splits LZ4's sequential
-// and parallel halves:
+// are almost all 4-5 byte matches).  A decoder that executes those sequences one at a time with
+// the whole wave (the project's first, since retired) has ~5 of 64 lanes do useful work and pays a
+// chain of read-lanes, LDS round trips and barriers per sequence (PMC: ~450 SIMD cycles).  This
+// decoder keeps one wave per chunk (full occupancy) but splits LZ4's sequential and parallel
+// halves:
 //
 //   parse    the token stream is walked with uniform (scalar) control flow, reading bytes from a
 //            wave-wide register window; each sequence becomes one record {gap, literal length,
@@ -21,41 +21,33 @@
 //            interleaved byte (4 j + group) on store.
 //
 // Lengths/offsets are validated in the execute step (lane-parallel) before any byte moves.
-// Clipped launches keep using the LDS-ring decoder.  Host oracle: csrc/core/lz4.cpp, compared
-// bit-exactly in tests/test_gpu_kernels.py.
+// A launch clipped to a byte window of dst runs the one-wave kernel's clipped instantiation: a chunk
+// the window cuts decodes into a slot of the launch's clip scratch and its part inside the window is
+// copied out.  Host oracle: csrc/core/lz4.cpp, compared bit-exactly in tests/test_gpu_kernels.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <string>
 
 #include "blake3_dev.h"
-#include "lz4win.h"
 #include "wave64.h"
 #include "zgpu.h"
 
 namespace {
 
-using zgw::Win;
-using zgw::load_u8_coherent;
-using zgw::win_init;
-using zgw::win_lane_u8;
-using zgw::win_seek;
-using zgw::win_u8;
+using zwv::kMaxChunk;
+using zwv::lane_id;
+using zwv::load_u8_coherent;
+using zwv::report;
 using zwv::scan_add;
 using zwv::scan_max;
 
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
-constexpr uint32_t kMaxChunk = 128u * 1024u;
 constexpr uint32_t kMaxRecsPerSeq = 8;  // 1 + 2 literal splits + 4 match splits (<= 128 KiB), + 1 spare
 constexpr uint32_t kFlushAbove = kWave - kMaxRecsPerSeq;
 constexpr uint32_t kRing = 4096;  // LDS history per wave (power of two): 8 waves / SIMD stay resident
 
-__device__ __forceinline__ void report(unsigned long long* err, uint32_t code, uint32_t idx) {
-  if (err) atomicCAS(err, 0ull, (static_cast<unsigned long long>(code) << 32) | idx);
-}
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint64_t uni64(uint64_t v) {
   return uint64_t(uni(uint32_t(v))) | (uint64_t(uni(uint32_t(v >> 32))) << 32);
@@ -544,26 +536,71 @@ __device__ uint32_t decode_chunk(Ctx& X, uint32_t lane) {
   return X.obase == X.ulen ? 0u : uint32_t(ZG_ERR_SIZE);
 }
 
+// Starts of BG4 groups 1-3 in the grouped stream of a ulen-byte chunk (groups 0 .. ulen % 4 - 1
+// hold one byte more).
+__device__ __forceinline__ void bg4_starts(uint32_t ulen, uint32_t& g1, uint32_t& g2, uint32_t& g3) {
+  const uint32_t q = ulen >> 2, r = ulen & 3;
+  g1 = q + (r > 0 ? 1u : 0u);
+  g2 = g1 + q + (r > 1 ? 1u : 0u);
+  g3 = g2 + q + (r > 2 ? 1u : 0u);
+}
+
+// What the decode kernels share of their chunk front end.
+// uniform_chunk: descriptor c, made wave-uniform.
+// fill_ctx: the Ctx of a chunk whose descriptor passed the kernel's checks -- all but the LDS
+// pointers heads / ring / pf, which are the kernel's.
+// The checks between the two (stored chunk, ZG_ERR_RANGE, ZG_ERR_CAPACITY, and who reports) stand in
+// each kernel: they are a few cold lines, but how they are shaped decides the register allocation of
+// the parse loops after them, so each kernel keeps the shape it is measured with
+// (profiles/lz4_one_family/README.md).
+__device__ __forceinline__ ZgChunk uniform_chunk(const ZgChunk* chunks, int c) {
+  ZgChunk ch = chunks[c];
+  // the descriptor is wave-uniform: say so, so the whole parse runs on SGPRs / the scalar unit
+  // (a vector load would otherwise make every derived position a VGPR and every branch divergent)
+  ch.src = uni64(ch.src);
+  ch.dst = uni64(ch.dst);
+  ch.clen = uni(ch.clen);
+  ch.ulen = uni(ch.ulen);
+  ch.scheme = uni(ch.scheme);
+  return ch;
+}
+
+__device__ __forceinline__ void fill_ctx(Ctx& X, const uint8_t* src, uint8_t* dst, const ZgChunk& ch) {
+  X.pay = src + ch.src;
+  X.out = dst + ch.dst;
+  X.clen = ch.clen;
+  X.ulen = ch.ulen;
+  X.bg4 = ch.scheme == 2;
+  bg4_starts(ch.ulen, X.g1, X.g2, X.g3);
+  X.k0 = uint32_t(reinterpret_cast<uintptr_t>(X.pay) & 3);
+  X.obase = 0;
+}
+
+// A chunk cut by the clip window decodes into one of two slots of the launch's clip scratch: the
+// chunk that starts before the window in the first, the one that ends after it in the second.
+constexpr uint32_t kClipSlot = kMaxChunk + 256;
+static_assert(2 * kClipSlot == ZG_CLIP_SCRATCH_BYTES, "clip scratch layout");
+
 // amdgpu_waves_per_eu(8): keep 8 waves per SIMD (<= 64 VGPRs).  The decoder is occupancy-bound
 // (profiles/lz4_records_r3.md), and with the wide literal copy inlined the register allocator
 // otherwise settled on 127 VGPRs = 4 waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage).
+//
+// kClip: only bytes [clip_lo, clip_hi) of dst are written.  A chunk outside the window is skipped
+// (after its descriptor checks), one inside decodes in place, and one the window cuts decodes
+// whole into its scratch slot (BG4 included: bmap is relative to X.out) and, once it has decoded
+// without error, its part inside the window is copied out.
+template <bool kClip>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_lz4_batched(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                      const ZgChunk* __restrict__ chunks, int n_chunks,
-                                                     unsigned long long* err, uint64_t src_n, uint64_t dst_n) {
+                                                     unsigned long long* err, uint64_t src_n, uint64_t dst_n,
+                                                     uint64_t clip_lo, uint64_t clip_hi, uint8_t* clip_scratch) {
   __shared__ uint32_t heads[kWavesPerBlock][kWave];
   __shared__ __attribute__((aligned(16))) uint8_t rings[kWavesPerBlock][kRing];
   const uint32_t lane = lane_id();
   const int wave = int(uni(threadIdx.x >> 6));
   const int stride = int(gridDim.x) * kWavesPerBlock;
   for (int c = int(uni(blockIdx.x * kWavesPerBlock + uint32_t(wave))); c < n_chunks; c += stride) {
-    ZgChunk ch = chunks[c];
-    // the descriptor is wave-uniform: say so, so the whole parse runs on SGPRs / the scalar unit
-    // (a vector load would otherwise make every derived position a VGPR and every branch divergent)
-    ch.src = uni64(ch.src);
-    ch.dst = uni64(ch.dst);
-    ch.clen = uni(ch.clen);
-    ch.ulen = uni(ch.ulen);
-    ch.scheme = uni(ch.scheme);
+    const ZgChunk ch = uniform_chunk(chunks, c);
     if (ch.scheme == 0) continue;
     if (ch.src + ch.clen > src_n || ch.dst + ch.ulen > dst_n) {
       if (lane == 0) report(err, ZG_ERR_RANGE, uint32_t(c));
@@ -574,21 +611,31 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
       continue;
     }
     Ctx X;
-    X.pay = src + ch.src;
-    X.out = dst + ch.dst;
-    X.clen = ch.clen;
-    X.ulen = ch.ulen;
-    X.bg4 = ch.scheme == 2;
-    const uint32_t q = ch.ulen >> 2, r = ch.ulen & 3;
-    X.g1 = q + (r > 0 ? 1u : 0u);
-    X.g2 = X.g1 + q + (r > 1 ? 1u : 0u);
-    X.g3 = X.g2 + q + (r > 2 ? 1u : 0u);
-    X.k0 = uint32_t(reinterpret_cast<uintptr_t>(X.pay) & 3);
-    X.obase = 0;
+    fill_ctx(X, src, dst, ch);
     X.heads = heads[wave];
     X.ring = rings[wave];
+    uint8_t* to = nullptr;  // (kClip) a cut chunk: where its bytes inside the window go,
+    uint32_t from = 0, n = 0;  // their offset in the chunk and their count
+    if (kClip) {
+      const uint64_t at = ch.dst, end = at + ch.ulen;
+      const uint64_t lo = at > clip_lo ? at : clip_lo, hi = end < clip_hi ? end : clip_hi;
+      if (lo >= hi) continue;
+      if (lo != at || hi != end) {
+        X.out = clip_scratch + (at < clip_lo ? 0u : kClipSlot);
+        to = dst + lo;
+        from = uint32_t(lo - at);
+        n = uint32_t(hi - lo);
+      }
+    }
     const uint32_t code = decode_chunk(X, lane);
-    if (code && lane == 0) report(err, code, uint32_t(c));
+    if (code) {
+      if (lane == 0) report(err, code, uint32_t(c));
+      continue;
+    }
+    if (kClip && to) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slot's bytes are in L2
+      for (uint32_t i = lane; i < n; i += kWave) to[i] = uint8_t(load_u8_coherent(X.out + from + i));
+    }
   }
 }
 
@@ -808,12 +855,9 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8))
       ++tk;
     }
     if (c >= n_chunks) break;
-    ZgChunk ch = A->chunks[c];
-    ch.src = uni64(ch.src);
-    ch.dst = uni64(ch.dst);
-    ch.clen = uni(ch.clen);
-    ch.ulen = uni(ch.ulen);
-    ch.scheme = uni(ch.scheme);
+    // (both waves; under the dynamic schedule the producer's ticket loop has settled every chunk
+    // that does not open, so only the static schedule's consumer reports here)
+    const ZgChunk ch = uniform_chunk(A->chunks, c);
     if (ch.scheme == 0) continue;
     auto bad_hash = [&]() {  // (consumer) a chunk that is not decoded hashes as all-ones
       if (!kHash) return;
@@ -831,17 +875,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8))
       continue;
     }
     Ctx X;
-    X.pay = A->src + ch.src;
-    X.out = A->dst + ch.dst;
-    X.clen = ch.clen;
-    X.ulen = ch.ulen;
-    X.bg4 = ch.scheme == 2;
-    const uint32_t qq = ch.ulen >> 2, r = ch.ulen & 3;
-    X.g1 = qq + (r > 0 ? 1u : 0u);
-    X.g2 = X.g1 + qq + (r > 1 ? 1u : 0u);
-    X.g3 = X.g2 + qq + (r > 2 ? 1u : 0u);
-    X.k0 = uint32_t(reinterpret_cast<uintptr_t>(X.pay) & 3);
-    X.obase = 0;
+    fill_ctx(X, A->src, A->dst, ch);
     X.heads = L.heads;
     X.ring = L.ring;
     // BG4 with a staging slice: decode the grouped stream contiguously into it (see ungroup_bg4)
@@ -1118,12 +1152,7 @@ __global__ void __launch_bounds__(256) k_lz4_exec(const uint8_t* __restrict__ sr
   const int wave = int(uni(threadIdx.x >> 6));
   const int stride = int(gridDim.x) * kWavesPerBlock;
   for (int c = int(uni(blockIdx.x * kWavesPerBlock + uint32_t(wave))); c < n_chunks; c += stride) {
-    ZgChunk ch = chunks[c];
-    ch.src = uni64(ch.src);
-    ch.dst = uni64(ch.dst);
-    ch.clen = uni(ch.clen);
-    ch.ulen = uni(ch.ulen);
-    ch.scheme = uni(ch.scheme);
+    const ZgChunk ch = uniform_chunk(chunks, c);
     if (ch.scheme == 0) continue;
     if (ch.src + ch.clen > src_n || ch.dst + ch.ulen > dst_n) {
       if (lane == 0) report(err, ZG_ERR_RANGE, uint32_t(c));
@@ -1134,17 +1163,7 @@ __global__ void __launch_bounds__(256) k_lz4_exec(const uint8_t* __restrict__ sr
       continue;
     }
     Ctx X;
-    X.pay = src + ch.src;
-    X.out = dst + ch.dst;
-    X.clen = ch.clen;
-    X.ulen = ch.ulen;
-    X.bg4 = ch.scheme == 2;
-    const uint32_t q = ch.ulen >> 2, r = ch.ulen & 3;
-    X.g1 = q + (r > 0 ? 1u : 0u);
-    X.g2 = X.g1 + q + (r > 1 ? 1u : 0u);
-    X.g3 = X.g2 + q + (r > 2 ? 1u : 0u);
-    X.k0 = uint32_t(reinterpret_cast<uintptr_t>(X.pay) & 3);
-    X.obase = 0;
+    fill_ctx(X, src, dst, ch);
     X.heads = heads[wave];
     X.ring = rings[wave];
     const uint32_t cnt = uni(counts[c]);
@@ -1155,15 +1174,70 @@ __global__ void __launch_bounds__(256) k_lz4_exec(const uint8_t* __restrict__ sr
 
 }  // namespace
 
-extern "C" hipError_t zg_lz4_batched_decode_grid(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
-                                                 const ZgChunk* chunks, int n_chunks, unsigned long long* err,
-                                                 int grid_cap, hipStream_t stream) {
+// Launch policy: every environment knob of the decoders, read here and nowhere else.  Each launch
+// reads them afresh (the tests flip them inside one process), once.
+struct Lz4Policy {
+  int pair;        // ZG_LZ4_PAIR: 1 (default) producer/consumer pairs, 0 the one-wave decoder, 2 ("auto")
+                   // pairs for launches of fewer than kPairBelow chunks
+  int grid_cap;    // ZG_LZ4_GRID: cap of the one-wave decoder's persistent grid (0: its default)
+  bool fused_hash;  // ZG_FUSED_HASH not 0, and ZG_LZ4_PAIR unset or exactly 1: the pairs hash what they decode
+  bool bg4_stage;   // ZG_BG4_STAGE not 0: BG4 chunks decode through the staging slices
+  bool dynamic;     // ZG_PAIR_DYNAMIC not 0: the pairs take chunks from a work counter
+  uint32_t prefetch;  // ZG_PAIR_PREFETCH not 0: the producer's stream prefetch
+  uint32_t debug;     // ZG_PAIR_DEBUG: diagnostics (k_lz4_pair `dbg`); unset in every real run
+};
+
+static bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return !(v && atoi(v) == 0);
+}
+
+static Lz4Policy lz4_policy() {
+  Lz4Policy p;
+  const char* v = getenv("ZG_LZ4_PAIR");
+  const std::string pair = v ? v : "1";
+  p.pair = pair == "auto" ? 2 : atoi(pair.c_str()) ? 1 : 0;
+  v = getenv("ZG_LZ4_GRID");
+  p.grid_cap = v ? atoi(v) : 0;
+  p.fused_hash = env_on("ZG_FUSED_HASH") && pair == "1";
+  p.bg4_stage = env_on("ZG_BG4_STAGE");
+  p.dynamic = env_on("ZG_PAIR_DYNAMIC");
+  p.prefetch = env_on("ZG_PAIR_PREFETCH") ? 1u : 0u;
+  v = getenv("ZG_PAIR_DEBUG");
+  p.debug = v ? uint32_t(atoi(v)) : 0u;
+  return p;
+}
+
+// The one-wave decoder: a persistent grid of at most grid_cap blocks of 4 waves (default 2048 =
+// 8 waves / SIMD).  clip_scratch != nullptr: the launch writes only dst bytes [clip_lo, clip_hi).
+static hipError_t launch_one_wave(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                                  const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
+                                  uint64_t clip_lo, uint64_t clip_hi, uint8_t* clip_scratch, hipStream_t stream) {
   if (n_chunks <= 0) return hipSuccess;
   if (grid_cap <= 0 || grid_cap >= 8192) grid_cap = 2048;
   const int blocks = (n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(k_lz4_batched, dim3(blocks < grid_cap ? blocks : grid_cap), dim3(256), 0, stream, src, dst,
-                     chunks, n_chunks, err, src_n, dst_n);
+  const dim3 grid(blocks < grid_cap ? blocks : grid_cap);
+  if (clip_scratch)
+    hipLaunchKernelGGL(k_lz4_batched<true>, grid, dim3(256), 0, stream, src, dst, chunks, n_chunks, err, src_n, dst_n,
+                       clip_lo, clip_hi, clip_scratch);
+  else
+    hipLaunchKernelGGL(k_lz4_batched<false>, grid, dim3(256), 0, stream, src, dst, chunks, n_chunks, err, src_n, dst_n,
+                       clip_lo, clip_hi, clip_scratch);
   return hipGetLastError();
+}
+
+extern "C" hipError_t zg_lz4_batched_decode_grid(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                                                 const ZgChunk* chunks, int n_chunks, unsigned long long* err,
+                                                 int grid_cap, hipStream_t stream) {
+  return launch_one_wave(src, src_n, dst, dst_n, chunks, n_chunks, err, grid_cap, 0, dst_n, nullptr, stream);
+}
+
+extern "C" hipError_t zg_lz4_decode_clipped(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                                            const ZgChunk* chunks, int n_chunks, uint64_t clip_lo, uint64_t clip_hi,
+                                            uint8_t* clip_scratch, unsigned long long* err, hipStream_t stream) {
+  if (clip_scratch == nullptr) return hipErrorInvalidValue;
+  return launch_one_wave(src, src_n, dst, dst_n, chunks, n_chunks, err, lz4_policy().grid_cap, clip_lo, clip_hi,
+                         clip_scratch, stream);
 }
 
 constexpr int kPairGrid = 4096;  // 4096 pairs = 8 waves / SIMD
@@ -1177,42 +1251,28 @@ extern "C" size_t zg_lz4_stage_bytes(int n_chunks) {
   return size_t(n_chunks < kPairGrid ? n_chunks : kPairGrid) * kMaxChunk + kWorkBytes;
 }
 
-static bool dynamic_enabled() {
-  const char* v = getenv("ZG_PAIR_DYNAMIC");  // read per launch: A/B of the chunk schedule
-  return !(v && atoi(v) == 0);
-}
-
-static uint32_t pair_debug() {
-  const char* v = getenv("ZG_PAIR_DEBUG");  // diagnostics (k_lz4_pair `dbg`); unset in every real run
-  return v ? uint32_t(atoi(v)) : 0u;
-}
-
-static bool stage_enabled() {
-  const char* v = getenv("ZG_BG4_STAGE");  // read per launch: tests A/B both paths in one process
-  return !(v && atoi(v) == 0);
-}
-
-extern "C" hipError_t zg_lz4_pair_decode_hash_staged(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
-                                                     const ZgChunk* chunks, int n_chunks, unsigned long long* err,
-                                                     int grid_cap, uint8_t* hashes, uint64_t* sizes, uint8_t* stage,
-                                                     size_t stage_bytes, hipStream_t stream) {
+// The pair decoder: grid_cap pairs at most (0 = kPairGrid).  hashes (or null): hash every decoded
+// chunk.  stage (zg_lz4_stage_bytes(n) of device memory, or null): BG4 staging slices, followed by
+// the dynamic schedule's work counter.
+static hipError_t launch_pair(const Lz4Policy& pol, const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                              const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
+                              uint8_t* hashes, uint64_t* sizes, uint8_t* stage, size_t stage_bytes,
+                              hipStream_t stream) {
   if (n_chunks <= 0) return hipSuccess;
   if (grid_cap <= 0 || grid_cap > 8192) grid_cap = kPairGrid;
   const int grid = n_chunks < grid_cap ? n_chunks : grid_cap;
   // the dynamic schedule's work counter lives in the scratch right after the staging slices (the
   // scratch is this pipeline's: its launches are ordered on one stream), zeroed before the launch
   uint32_t* work = nullptr;
-  if (stage && dynamic_enabled() && stage_bytes >= size_t(grid) * kMaxChunk + kWorkBytes) {
+  if (stage && pol.dynamic && stage_bytes >= size_t(grid) * kMaxChunk + kWorkBytes) {
     work = reinterpret_cast<uint32_t*>(stage + size_t(grid) * kMaxChunk);
     const hipError_t e = hipMemsetAsync(work, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
   }
-  if (!stage_enabled() || !stage || stage_bytes < size_t(grid) * kMaxChunk) stage = nullptr;
-  const uint32_t dbg = pair_debug();
-  const char* pfv = getenv("ZG_PAIR_PREFETCH");  // read per launch: A/B of the stream prefetch
-  const uint32_t prefetch = (pfv && atoi(pfv) == 0) ? 0u : 1u;
-  const PairArgs args{src, dst, chunks, err, src_n, dst_n, hashes, sizes, stage, work, n_chunks, dbg, prefetch};
-  if (hashes && dbg)
+  if (!pol.bg4_stage || !stage || stage_bytes < size_t(grid) * kMaxChunk) stage = nullptr;
+  const PairArgs args{src,   dst,   chunks, err,      src_n,     dst_n,       hashes,
+                      sizes, stage, work,   n_chunks, pol.debug, pol.prefetch};
+  if (hashes && pol.debug)
     hipLaunchKernelGGL((k_lz4_pair<true, true>), dim3(grid), dim3(2 * kWave), 0, stream, args);
   else if (hashes)
     hipLaunchKernelGGL((k_lz4_pair<true, false>), dim3(grid), dim3(2 * kWave), 0, stream, args);
@@ -1221,43 +1281,31 @@ extern "C" hipError_t zg_lz4_pair_decode_hash_staged(const uint8_t* src, uint64_
   return hipGetLastError();
 }
 
-extern "C" hipError_t zg_lz4_pair_decode_hash(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
-                                              const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
-                                              uint8_t* hashes, uint64_t* sizes, hipStream_t stream) {
-  return zg_lz4_pair_decode_hash_staged(src, src_n, dst, dst_n, chunks, n_chunks, err, grid_cap, hashes, sizes,
-                                        nullptr, 0, stream);
-}
-
 extern "C" hipError_t zg_lz4_pair_decode(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
                                          const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
                                          hipStream_t stream) {
-  return zg_lz4_pair_decode_hash(src, src_n, dst, dst_n, chunks, n_chunks, err, grid_cap, nullptr, nullptr, stream);
+  return launch_pair(lz4_policy(), src, src_n, dst, dst_n, chunks, n_chunks, err, grid_cap, nullptr, nullptr, nullptr,
+                     0, stream);
+}
+
+// Decode only, by the decoder the policy picks.  With the wide literal copies and both kernels held
+// at 8 waves per SIMD, pairs win at every size (BG4 bf16, kbench k3pair, one-wave -> pair: 128 MiB
+// 48 -> 78 GB/s, 256 MiB 82 -> 95, 512 MiB 95 -> 124, 1 GiB 123 -> 136;
+// profiles/r4/kbench_k3_wide_r4j.jsonl).  Before them the one-wave decoder won from ~10 k chunks
+// up (profiles/r4/kbench_k3pair_sizes_r4e.jsonl), which is what `auto` keeps.
+constexpr int kPairBelow = 10240;
+
+static hipError_t decode_plain(const Lz4Policy& pol, const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                               const ZgChunk* chunks, int n_chunks, unsigned long long* err, hipStream_t stream) {
+  if (pol.pair == 1 || (pol.pair == 2 && n_chunks < kPairBelow))
+    return launch_pair(pol, src, src_n, dst, dst_n, chunks, n_chunks, err, 0, nullptr, nullptr, nullptr, 0, stream);
+  return launch_one_wave(src, src_n, dst, dst_n, chunks, n_chunks, err, pol.grid_cap, 0, dst_n, nullptr, stream);
 }
 
 extern "C" hipError_t zg_lz4_batched_decode(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
                                             const ZgChunk* chunks, int n_chunks, unsigned long long* err,
                                             hipStream_t stream) {
-  // ZG_LZ4_GRID caps the persistent grid (occupancy experiments); default 2048 blocks = 8 waves/SIMD.
-  static const int grid_cap = [] {
-    const char* v = getenv("ZG_LZ4_GRID");
-    return v ? atoi(v) : 0;
-  }();
-  // ZG_LZ4_PAIR: 1 (default) = producer/consumer pairs, 0 = the one-wave decoder, auto = pairs for
-  // launches of fewer than kPairBelow chunks.  With the wide literal copies and both kernels held at
-  // 8 waves per SIMD, pairs win at every size (BG4 bf16, kbench k3pair, one-wave -> pair: 128 MiB
-  // 48 -> 78 GB/s, 256 MiB 82 -> 95, 512 MiB 95 -> 124, 1 GiB 123 -> 136;
-  // profiles/r4/kbench_k3_wide_r4j.jsonl).  Before them the one-wave decoder won from ~10 k chunks
-  // up (profiles/r4/kbench_k3pair_sizes_r4e.jsonl), which is what `auto` keeps.
-  constexpr int kPairBelow = 10240;
-  static const int pair = [] {
-    const char* v = getenv("ZG_LZ4_PAIR");
-    if (!v) return 1;
-    if (std::string(v) == "auto") return 2;
-    return atoi(v) ? 1 : 0;
-  }();
-  if (pair == 1 || (pair == 2 && n_chunks < kPairBelow))
-    return zg_lz4_pair_decode(src, src_n, dst, dst_n, chunks, n_chunks, err, 0, stream);
-  return zg_lz4_batched_decode_grid(src, src_n, dst, dst_n, chunks, n_chunks, err, grid_cap, stream);
+  return decode_plain(lz4_policy(), src, src_n, dst, dst_n, chunks, n_chunks, err, stream);
 }
 
 // Decode for an unclipped ingest launch.  With the pair decoder (the default) and ZG_FUSED_HASH not 0,
@@ -1267,14 +1315,10 @@ extern "C" hipError_t zg_lz4_decode_ingest(const uint8_t* src, uint64_t src_n, u
                                            const ZgChunk* chunks, int n_chunks, unsigned long long* err,
                                            uint8_t* hashes, uint64_t* sizes, int* hashed, uint8_t* stage,
                                            size_t stage_bytes, hipStream_t stream) {
-  const char* v = getenv("ZG_FUSED_HASH");  // read per launch: tests A/B both paths in one process
-  const char* p = getenv("ZG_LZ4_PAIR");
-  const bool fuse = !(v && atoi(v) == 0) && !(p && std::string(p) != "1");
-  *hashed = 0;
-  if (!fuse || !hashes) return zg_lz4_batched_decode(src, src_n, dst, dst_n, chunks, n_chunks, err, stream);
-  *hashed = 1;
-  return zg_lz4_pair_decode_hash_staged(src, src_n, dst, dst_n, chunks, n_chunks, err, 0, hashes, sizes, stage,
-                                        stage_bytes, stream);
+  const Lz4Policy pol = lz4_policy();
+  *hashed = pol.fused_hash && hashes;
+  if (!*hashed) return decode_plain(pol, src, src_n, dst, dst_n, chunks, n_chunks, err, stream);
+  return launch_pair(pol, src, src_n, dst, dst_n, chunks, n_chunks, err, 0, hashes, sizes, stage, stage_bytes, stream);
 }
 
 extern "C" size_t zg_lz4_rec_scratch_bytes(int n_chunks, uint64_t src_n) {

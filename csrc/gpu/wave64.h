@@ -1,10 +1,28 @@
-// Wave64 cross-lane primitives for gfx950 (CDNA4): DPP inclusive scans, wave-cooperative copy.
+// Wave64 device helpers for gfx950 (CDNA4) shared by the ingest kernels (ingest.hip, lz4seq.hip):
+// lane id, the error report, DPP inclusive scans, wave-cooperative copy, an L2-coherent byte load.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace zwv {
+
+constexpr uint32_t kMaxChunk = 128u * 1024u;  // Xet CDC maximum chunk size
+
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63; }
+
+// Error word (zgpu.h): code << 32 | index; the first error of a launch wins.
+__device__ __forceinline__ void report(unsigned long long* err, uint32_t code, uint32_t idx) {
+  if (err) atomicCAS(err, 0ull, (static_cast<unsigned long long>(code) << 32) | idx);
+}
+
+// L2-coherent byte load (bypasses this CU's L1, which never sees its own earlier stores).
+__device__ __forceinline__ uint32_t load_u8_coherent(const uint8_t* p) {
+  const uint32_t k = uint32_t(reinterpret_cast<uintptr_t>(p) & 3);
+  uint32_t* w = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(p - k));
+  const uint32_t v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return (v >> (8 * k)) & 0xFF;
+}
 
 // row_shr:1/2/4/8 within 16-lane rows, then row_bcast:15 / row_bcast:31 across rows (gfx9 DPP):
 // six VALU ops per scan instead of six LDS permutes.

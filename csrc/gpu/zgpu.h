@@ -64,8 +64,9 @@ hipError_t zg_index_terms(const uint8_t* src, const ZgTerm* terms, int n_terms, 
 // one per concurrently running launch): compressed chunks that straddle the window decode there
 // before their clipped part is copied out.  Without it such a launch returns hipErrorInvalidValue.
 #define ZG_CLIP_SCRATCH_BYTES (2u * (128u * 1024u + 256u))
-// Unclipped launches decode LZ4 chunks with the batched decoder (lz4seq.hip: scalar parse into
-// lane registers + lane-parallel execute); clipped ones with the LDS-ring decoder (ingest.hip).
+// LZ4 chunks decode with the batched decoder (lz4seq.hip: scalar parse into lane registers +
+// lane-parallel execute): unclipped launches by zg_lz4_batched_decode, clipped ones by the one-wave
+// kernel's clipped instantiation (zg_lz4_decode_clipped).
 // K4 parallel header walk: candidate scan over the span [0, src_n) of src + per-term sort/link in
 // LDS; a term whose candidates are not exactly its chunk chain takes the serial walk (same records
 // and errors as zg_index_terms).  Terms sorted by src.  scratch: zg_index_scratch_bytes(n_terms)
@@ -93,6 +94,11 @@ hipError_t zg_lz4_pair_decode(const uint8_t* src, uint64_t src_n, uint8_t* dst, 
 hipError_t zg_lz4_batched_decode_grid(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
                                       const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
                                       hipStream_t stream);
+// The LZ4/BG4 half of a clipped zg_place_chunks: the one-wave decoder writing only dst bytes
+// [clip_lo, clip_hi); clip_scratch as for zg_place_chunks (null: hipErrorInvalidValue).
+hipError_t zg_lz4_decode_clipped(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
+                                 const ZgChunk* chunks, int n_chunks, uint64_t clip_lo, uint64_t clip_hi,
+                                 uint8_t* clip_scratch, unsigned long long* err, hipStream_t stream);
 // K1 keyed BLAKE3 of placed chunks (hashes[hash_index_base + c], sizes likewise when non-null) or of
 // raw (offset, len) messages (key_mode 0 Xet data key, 1 node key, 2 plain, 3 zero key; a message
 // over 128 KiB gets an all-ones hash).  With `scratch` (>= zg_hash_scratch_bytes(n, total message
@@ -112,22 +118,18 @@ hipError_t zg_hash_chunks_flat(const uint8_t* dst, uint64_t dst_n, const ZgChunk
 hipError_t zg_hash_ranges_flat(const uint8_t* buf, const uint64_t* offsets, const uint32_t* lens, int n,
                                uint8_t* hashes, int key_mode, uint8_t* scratch, size_t scratch_bytes,
                                hipStream_t stream);
-// Fused K3a + K1: uncompressed chunks are copied src -> dst by the hashing waves themselves (and
-// hashed from src); compressed ones must already be decoded into dst.  Descriptors out of bounds are
-// not placed, hash over empty leaves (never their real hash) and set ZG_ERR_RANGE (chunk index) in `err` (may be null).
-hipError_t zg_lz4_pair_decode_hash(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
-                                   const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
-                                   uint8_t* hashes, uint64_t* sizes, hipStream_t stream);
+// Decode of an unclipped ingest launch; *hashed = 1 when the decoder also hashed every compressed
+// chunk (hashes[c], sizes[c]: the pair decoder with ZG_FUSED_HASH not 0), else 0.
 // `stage` (>= zg_lz4_stage_bytes(n) of device memory, or null): BG4 chunks decode their grouped
 // stream there and are written to dst once, whole lines at a time (ZG_BG4_STAGE=0 turns it off).
 hipError_t zg_lz4_decode_ingest(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n, const ZgChunk* chunks,
                                 int n_chunks, unsigned long long* err, uint8_t* hashes, uint64_t* sizes, int* hashed,
                                 uint8_t* stage, size_t stage_bytes, hipStream_t stream);
 size_t zg_lz4_stage_bytes(int n_chunks);
-hipError_t zg_lz4_pair_decode_hash_staged(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
-                                          const ZgChunk* chunks, int n_chunks, unsigned long long* err, int grid_cap,
-                                          uint8_t* hashes, uint64_t* sizes, uint8_t* stage, size_t stage_bytes,
-                                          hipStream_t stream);
+// Fused K3a + K1: uncompressed chunks are copied src -> dst by the hashing waves themselves (and
+// hashed from src); compressed ones must already be decoded into dst (_raw: and hashed, so they are
+// skipped).  Descriptors out of bounds are not placed, hash over empty leaves (never their real
+// hash) and set ZG_ERR_RANGE (chunk index) in `err` (may be null).
 hipError_t zg_place_hash_flat_raw(const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n,
                                   const ZgChunk* chunks, int n_chunks, unsigned long long* err, uint8_t* hashes,
                                   uint64_t* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t stream);

@@ -237,3 +237,103 @@ def test_malformed_frame_is_reported(case, scheme):
         masked = got[:lo] + bytes(image[lo:hi]) + got[hi:]
         assert masked == bytes(image), (dec, _first_diff(masked, image, rec, names))
     assert len({err for _, _, err in outs}) == 1
+
+
+# ------------------------------------------------------------------------------------------------
+# clipped launches (place_chunks with a window narrower than dst): the one-wave kernel's clipped
+# instantiation -- a chunk the window cuts decodes into a slot of the clip scratch, and its part
+# inside the window is copied out
+# ------------------------------------------------------------------------------------------------
+SENTINEL = 0xC3
+
+
+def _place_clipped(src, src_n, rec, dst_total, dst_n, lo, hi):
+    """One clipped place_chunks launch into FILL-ed storage; returns (dst storage bytes, error word)."""
+    H = ops.hip()
+    dst = torch.full((dst_total,), FILL, dtype=torch.uint8, device=DEV)
+    chunks = torch.from_numpy(rec.view(np.uint8).copy()).to(DEV)
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    scratch = torch.full((H.CLIP_SCRATCH_BYTES,), SENTINEL, dtype=torch.uint8, device=DEV)
+    H.place_chunks(src.data_ptr(), src_n, dst.data_ptr(), dst_n, chunks.data_ptr(), len(rec), lo, hi, err.data_ptr(),
+                   torch.cuda.current_stream().cuda_stream, scratch.data_ptr())
+    torch.cuda.synchronize()
+    return dst.cpu().numpy().tobytes(), int(err.item())
+
+
+def _clipped_image(image, lo, hi):
+    return bytes([FILL]) * lo + bytes(image[lo:hi]) + bytes([FILL]) * (len(image) - hi)
+
+
+def _windows(rec):
+    """The clip windows of test_clipped_place_matches_reference, from the chunk records."""
+    at = [int(r["dst"]) for r in rec]
+    ul = [int(r["ulen"]) for r in rec]
+    n = len(rec)
+    inner = [i for i in range(1, n - 1) if ul[i] >= 3]  # chunks with a byte strictly inside
+    a, b = inner[0], inner[-1]
+    big = max(range(n), key=lambda i: ul[i])
+    mid = inner[len(inner) // 2]
+    assert a < b and ul[big] >= 16 and at[mid] - (at[mid - 1] + ul[mid - 1]) >= 3
+    return {
+        "two_cut": (at[a] + ul[a] // 2, at[b] + (ul[b] + 1) // 2),        # both slots in one launch
+        "one_cut_twice": (at[big] + ul[big] // 3, at[big] + ul[big] - ul[big] // 5),
+        "one_byte": (at[mid] + ul[mid] - 2, at[mid] + ul[mid] - 1),
+        "on_chunk_edges": (at[a], at[b] + ul[b]),                        # a clipped launch, no chunk cut
+        "in_gap": (at[mid] - 2, at[mid]),                                # nothing is written
+    }
+
+
+WINDOW_NAMES = ("two_cut", "one_cut_twice", "one_byte", "on_chunk_edges", "in_gap")
+_clip_inputs = {}
+
+
+def _clip_input(fam, scheme):
+    """The family's layout and its device source, built once per (family, scheme) and not modified."""
+    if (fam, scheme) not in _clip_inputs:
+        cases = S.family(fam)
+        src, src_n, rec, image, dst_n, _ = _layout([(scheme, c.frame, len(c.data), _want(c, scheme)) for c in cases],
+                                                   rot=scheme)
+        _clip_inputs[fam, scheme] = (_dev(src), src_n, rec, bytes(image), dst_n, [c.name for c in cases])
+    return _clip_inputs[fam, scheme]
+
+
+@pytest.mark.parametrize("window", WINDOW_NAMES)
+@pytest.mark.parametrize("scheme", [1, 2])
+@pytest.mark.parametrize("fam", ["frame_shapes", "wide", "ring"])
+def test_clipped_place_matches_reference(fam, scheme, window):
+    """A clipped launch over the whole family: error word 0, dst[lo:hi] byte-exact, every byte outside
+    [lo, hi) (pad included) untouched.  frame_shapes: multi-block frames, stored blocks, checksums;
+    wide: long batches and wide literal copies into a slot, BG4 group boundaries, the 131072-byte chunk
+    that fills a slot; ring: far sources read back from a slot."""
+    src, src_n, rec, image, dst_n, names = _clip_input(fam, scheme)
+    lo, hi = _windows(rec)[window]
+    assert 0 < lo < hi < dst_n
+    if window == "one_cut_twice" and fam == "wide":
+        assert hi - lo > 60000 and max(int(r["ulen"]) for r in rec) == 131072
+    got, err = _place_clipped(src, src_n, rec, len(image), dst_n, lo, hi)
+    assert err == 0, (hex(err), names[err & 0xFFFFFFFF])
+    want = _clipped_image(image, lo, hi)
+    assert got == want, _first_diff(got, want, rec, names)
+
+
+@pytest.mark.parametrize("scheme", [1, 2])
+@pytest.mark.parametrize("case", S.malformed(), ids=lambda m: m[0])
+def test_clipped_malformed_is_reported(case, scheme):
+    """The layout of test_malformed_frame_is_reported under a window that cuts the bad chunk at lo (and
+    the last chunk at hi): the error word is the unclipped decoders', the good neighbours inside the
+    window are exact, and nothing else is written -- a cut chunk that fails is not copied out of its
+    slot, so not even the bad chunk's own range."""
+    name, frm, ulen, code = case
+    good = S.family("block_tail")[:5] + S.family("frame_shapes")[:5]
+    bad_at = 6
+    chunks = [(scheme, c.frame, len(c.data), _want(c, scheme)) for c in good]
+    chunks.insert(bad_at, (scheme, frm, ulen, None))
+    names = [c[3] is None and name or "good" for c in chunks]
+    src, src_n, rec, image, dst_n, _ = _layout(chunks)
+    lo = int(rec[bad_at]["dst"]) + ulen // 2
+    hi = int(rec[-1]["dst"]) + max(1, int(rec[-1]["ulen"]) // 2)
+    assert int(rec[bad_at]["dst"]) < lo < int(rec[bad_at]["dst"]) + ulen
+    got, err = _place_clipped(_dev(src), src_n, rec, len(image), dst_n, lo, hi)
+    assert err == (code << 32) | bad_at, hex(err)
+    want = _clipped_image(image, lo, hi)  # (the image holds FILL over the bad chunk's range)
+    assert got == want, _first_diff(got, want, rec, names)

@@ -289,7 +289,7 @@ def ingest_terms(src: torch.Tensor, dst: torch.Tensor, terms: np.ndarray, hashes
     terms: TERM_DTYPE records; chunk_base indexes `hashes` (uint8 [N, 32]) relative to hash_base.
     clip: optional (lo, hi) arena byte window this rank owns: bytes outside are not written, and
     the hashes of chunks not entirely inside the window are unspecified.
-    LZ4 chunks take the batched decoder (lz4seq.hip) unless clipped (LDS-ring decoder).
+    LZ4 chunks take the batched decoder (lz4seq.hip); a clipped batch its one-wave clipped kernel.
     fused (default: ZEST_FUSED_INGEST != 0): unclipped batches run decode + one fused place/hash
     pass (zg_ingest_chunks) instead of place then hash; `has_compressed=False` skips the decoder.
     """
