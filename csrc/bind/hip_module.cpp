@@ -282,4 +282,12 @@ PYBIND11_MODULE(_hip, m) {
           "zg_serve_pack");
   }, py::arg("src_table"), py::arg("ser_end_table"), py::arg("n"), py::arg("lo"), py::arg("hi"), py::arg("out"),
      py::arg("stream"));
+  m.attr("SLICE_ROWS") = int(ZG_SLICE_ROWS);
+  m.def("slice_gather", [](uintptr_t src, uintptr_t table, uint32_t n, uint64_t dst_total, uintptr_t dst,
+                           uintptr_t st) {
+    check(zg_slice_gather(P<const uint8_t>(src), P<const uint64_t>(table), n, dst_total, P<uint8_t>(dst), S(st)),
+          "zg_slice_gather");
+  }, py::arg("src"), py::arg("table"), py::arg("n"), py::arg("dst_total"), py::arg("dst"), py::arg("stream"),
+     "K10: table is a device block of SLICE_ROWS rows of n uint64 (src_off, run_bytes, src_stride, n_runs, "
+     "dst_off, dst_end), pre-validated by the caller (zest_amd.ops.slice_gather)");
 }

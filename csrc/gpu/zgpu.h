@@ -178,6 +178,25 @@ hipError_t zg_pack_chunks(const uint8_t* data, const uint64_t* data_off, const u
 hipError_t zg_serve_pack(const uint64_t* src, const uint64_t* ser_end, uint32_t n, uint64_t lo, uint64_t hi,
                          uint8_t* out, hipStream_t stream);
 
+// K10 (shard.hip): gather the kept slices of n tensors from src into a compact arena at dst.  table:
+// device block of ZG_SLICE_ROWS rows of n uint64 each.  Tensor i is n_runs[i] runs of run_bytes[i]
+// bytes, run r read at src + src_off[i] + r * src_stride[i] (any alignment, src_stride >= run_bytes),
+// laid end to end at dst + dst_off[i]; dst_end[i] = dst_off[i] + n_runs[i] * run_bytes[i].  Entries
+// are sorted by dst_off with disjoint outputs; dst and every dst_off are 16-byte aligned; zero-size
+// entries are legal.  dst_total = dst_end[n - 1].  Only the tensors' output bytes are written.  The
+// caller vouches for the table: nothing is checked on the device.
+enum {
+  ZG_SLICE_SRC_OFF = 0,
+  ZG_SLICE_RUN_BYTES = 1,
+  ZG_SLICE_SRC_STRIDE = 2,
+  ZG_SLICE_N_RUNS = 3,
+  ZG_SLICE_DST_OFF = 4,
+  ZG_SLICE_DST_END = 5,
+  ZG_SLICE_ROWS = 6
+};
+hipError_t zg_slice_gather(const uint8_t* src, const uint64_t* table, uint32_t n, uint64_t dst_total, uint8_t* dst,
+                           hipStream_t stream);
+
 // K8: pull each segment's bytes from a peer's IPC-mapped arena (xGMI) into this GPU's arena;
 // every segment is read concurrently.  src[i] and dst[i] must be congruent mod 16.
 enum { kZgMaxPeerSegs = 16 };

@@ -32,6 +32,40 @@ from zest_amd.synthetic import SyntheticWorld  # noqa: E402
 from zest_amd.testing import FakeHub  # noqa: E402
 
 
+def shard_runs(a, spec, world, hub, work, peer, total) -> list:
+    """Unsharded against sharded device pulls from the loopback HBM seeder, alternating, two rounds;
+    the first (untimed) pull warms connections, allocator and kernels."""
+    rank, n = (int(x) for x in a.shard.split("/"))
+    one_file = max(f.size for f in world.xet_files)
+    variants = [("unsharded", {}), (f"shard {rank}/{n}", {"shard": (rank, n)}),
+                (f"shard {rank}/{n}, scratch of one file", {"shard": (rank, n), "scratch_bytes": one_file})]
+    os.environ["ZEST_CACHE_WRITES"] = "0"
+    zest_amd._init()
+    runs = []
+    for rnd in range(-1, 2):
+        for vi, (name, kw) in enumerate(variants[:1] if rnd < 0 else variants):
+            os.environ.update(hub.env(str(work / f"shard{rnd}_{vi}")))
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            st = {}
+            t0 = time.time()
+            out = zest_amd.pull(spec.repo_id, device="cuda:0", peers=[peer], dht=False, threads=a.threads, stats=st, **kw)
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            r = {"variant": name, "round": rnd, "s": round(dt, 3), "file_gbps": round(total / dt / 1e9, 3),
+                 "peak_torch_bytes": torch.cuda.max_memory_allocated() - base,
+                 "kept_bytes": sum(v.numel() * v.element_size() for v in out.values()), "tensors": len(out)}
+            r.update({k: v for k, v in st.get("shard", {}).items() if k != "skipped_files"})
+            del out
+            if rnd >= 0:
+                runs.append(r)
+            print(f"[shard bench{' warm-up' if rnd < 0 else ''}] {json.dumps(r)}", flush=True)
+    os.environ.pop("ZEST_CACHE_WRITES")
+    return runs
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama-3.1-8b")
@@ -48,6 +82,10 @@ def main() -> int:
                          "'ZEST_GPU_WRITERS=1;ZEST_GPU_WRITERS=2,ZEST_GPU_WRITE_SLOTS=3'")
     ap.add_argument("--host-after", action="store_true",
                     help="time the host pull again after the GPU CLI configs (order check)")
+    ap.add_argument("--shard", default=None, metavar="R/N",
+                    help="compare the unsharded device pull with pull(shard=(R, N)) (built-in llama-tp plan), default "
+                         "scratch and a scratch of one file: each twice, alternating, no disk cache writes; records "
+                         "GB/s of file bytes pulled, gather_s and peak torch memory, then exits")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -76,6 +114,14 @@ def main() -> int:
                     "synthetic N(0,0.02) bf16 weights, real tensor shapes, BG4-LZ4 frames (stored/raw "
                     f"{float(world.chunk_clen.sum()) / float(world.chunk_len.sum()):.3f})")}
     try:
+        if a.shard:
+            res["shard_runs"] = shard_runs(a, spec, world, hub, work, peer, total)
+            res["seeder"] = srv.stats()
+            print(json.dumps(res), flush=True)
+            if a.out:
+                Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+                Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+            return 0
         if not a.skip_direct:
             # warm-up on the smallest Xet file (connections, allocator, kernels)
             zest_amd._init()

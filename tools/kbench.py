@@ -392,6 +392,54 @@ def main():
             H.host_free(host)
         del d_out
 
+    if want("slice_gather"):
+        # K10 slice_gather: one Llama-3.1-70B safetensors shard, rank 0 of 8 under the "llama-tp" plan,
+        # next to its roof (a device-to-device copy of the kept bytes: read N + write N) and to what it
+        # replaces (narrow(...).contiguous() per kept tensor); alternated, three rounds
+        from zest_amd import device as zdev
+        from zest_amd import models
+        from zest_amd.shard import Shard, plan_file
+
+        sf = models.get("llama-3.1-70b").shards()[1]
+        start, meta = zdev.parse_safetensors_header(sf.header)
+        plan = plan_file(start, meta, Shard(0, 8), sf.size)
+        kept = sum(t.nbytes for t in plan.tensors)
+        fbuf = arena if n >= sf.size else ops.padded_empty(sf.size, dev)
+        if fbuf is not arena:
+            ops.fill_synthetic(fbuf, 2, 0, 0)
+        fbuf = fbuf[:sf.size]
+        out = ops.padded_empty(plan.arena_bytes, dev)
+        flat = ops.padded_empty(kept, dev)
+        views = zdev.tensor_views(fbuf, start, meta)
+        acts = {t.name: Shard(0, 8).resolve(t.name, meta[t.name]["shape"], t.dtype) for t in plan.tensors}
+        tab = np.empty((H.SLICE_ROWS, len(plan.table)), dtype=np.uint64)
+        for k, f in enumerate(ops.SLICE_DTYPE.names):
+            tab[k] = plan.table[f]
+        tab[5] = tab[4] + tab[1] * tab[3]
+        tab_d = torch.from_numpy(tab.view(np.int64)).to(dev)
+
+        def torch_loop(copy=lambda t: t.contiguous()):
+            return [views[nm].clone() if act is None else copy(views[nm].narrow(act[0], act[1], act[2] - act[1]))
+                    for nm, act in acts.items()]
+
+        # contiguous() copies only the dim-1 slices: a dim-0 slice is contiguous already and stays a view
+        # into the file buffer, which then cannot be freed.  The clone loop gives every kept tensor its
+        # own memory, as the kernel does: that is the like-for-like row.
+        rows = (("torch_narrow_clone_loop", lambda: torch_loop(lambda t: t.clone(memory_format=torch.contiguous_format))),("slice_gather[ops]", lambda: ops.slice_gather(fbuf, plan.table, out)),
+                ("slice_gather[kernel]", lambda: H.slice_gather(fbuf.data_ptr(), tab_d.data_ptr(), tab.shape[1],
+                                                                int(tab[5, -1]), out.data_ptr(), st)),
+                ("d2d_copy_of_kept_bytes", lambda: flat.copy_(fbuf[:kept])),
+                ("torch_narrow_contiguous_loop", torch_loop))
+        for rnd in range(3):
+            for name, fn in rows:
+                ms = timed(fn, a.iters)
+                emit(kernel=name, round=rnd, bytes=kept, ms=ms, gbps=kept / ms / 1e6, file_bytes=sf.size,
+                     tensors=len(plan.tensors), sliced=sum(a_ is not None for a_ in acts.values()))
+        got = plan.views(out)
+        for nm, t in zip(acts, torch_loop()):
+            assert torch.equal(got[nm].view(torch.uint8), t.reshape(got[nm].shape).view(torch.uint8)), nm
+        del out, flat, tab_d, views, got
+
     if want("h2d"):
         pin = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()
         d = torch.empty(1 << 30, dtype=torch.uint8, device=dev)

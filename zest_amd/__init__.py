@@ -57,7 +57,8 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
          p2p: bool = True, peers=None, tracker=None, dht: bool = True, dht_bootstrap=None, include=None,
          group=None, repo_type: str = "model", verbose: bool = False, direct: bool | None = None,
          save_snapshot: bool = False, threads: int = 16, staging_bytes: int = 1 << 30, stats: dict | None = None,
-         exchange: str = "auto", round_bytes: int | None = None, seed=False):
+         exchange: str = "auto", round_bytes: int | None = None, seed=False, shard=None,
+         scratch_bytes: int | None = None):
     """Download `repo@revision` via zest.
 
     * default: returns the HF-cache snapshot directory (reference behaviour).
@@ -83,7 +84,25 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       are seeded to BEP XET peers straight from the HBM the returned tensors occupy -- no serialized
       copy, no disk (zest_amd.seed.ResidentSeedServer; `zest_amd.seed.active()` lists the servers,
       `zest_amd.seed.stop_all()` / `zest_amd.stop()` stop them).  Keep the tensors read-only meanwhile.
+    * shard=Shard(rank, world, plan) or (rank, world), device="cuda:N" / "cpu" direct pulls only: the
+      returned tensors are this rank's slices (tensor-parallel parts, a pipeline stage, its experts:
+      zest_amd.shard) and only they stay in device memory.  Every file is still pulled and verified
+      whole, through a reused scratch of `scratch_bytes` (default: the larger of the largest file and
+      16 GiB, never more than the files need), because a Xet file hash covers the whole file: this
+      bounds device memory, not network bytes.  Files in which the rank keeps nothing (per
+      model.safetensors.index.json) are not fetched.  `stats["shard"]` receives file_bytes, kept_bytes,
+      skipped_files, groups, scratch_bytes and gather_s.
     """
+    if shard is not None:
+        if device is None:
+            raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu'); a snapshot pull has no tensors "
+                             "to slice")
+        if device == "all":
+            raise ValueError("shard= is not supported with device='all': run one process per GPU with "
+                             "device='cuda:N' (a collective sharded pull does not exist yet)")
+        if direct is False:
+            raise ValueError("shard= is not supported with direct=False (the snapshot path): use the default "
+                             "device-direct pull")
     if seed is not False and seed is not None:
         if device == "all":
             raise ValueError("seed= is not supported with device='all' (swarm pulls): use a single device='cuda:N'")
@@ -112,7 +131,8 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
 
         return pull_to_device(repo, revision, device or "cuda:0", p2p=p2p, peers=peers, tracker=tracker, dht=dht,
                               dht_bootstrap=dht_bootstrap, repo_type=repo_type, save_snapshot=save_snapshot,
-                              threads=threads, staging_bytes=staging_bytes, include=include, seed=seed)
+                              threads=threads, staging_bytes=staging_bytes, include=include, seed=seed, shard=shard,
+                              scratch_bytes=scratch_bytes, stats=stats if shard is not None else None)
     from .device import load_snapshot
 
     res = _client.pull_detailed(repo, revision, **kw)

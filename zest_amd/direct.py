@@ -17,6 +17,16 @@ device bytes are also written to the HF cache snapshot so later `from_pretrained
 peers straight from the HBM the returned tensors live in (`zest_amd.seed.ResidentSeedServer`): no
 serialized second copy, no disk.  The server is kept in `zest_amd.seed.active()` until
 `zest_amd.seed.stop_all()`.  Treat the tensors as read-only while seeding.
+
+    tensors = pull_to_device("meta-llama/Llama-3.1-405B", device="cuda:3", shard=(3, 8))
+
+`shard=` (a `zest_amd.shard.Shard`, or (rank, world) for the built-in "llama-tp" plan): only this
+rank's tensor slices stay in device memory.  Files are still pulled and verified whole (a Xet file
+hash covers every chunk of the file) through one reused scratch of `scratch_bytes`, then
+`ops.slice_gather` copies the kept slices into a compact arena per file; files in which the rank
+keeps nothing (per `model.safetensors.index.json`) are not fetched.  It bounds device memory, not
+network bytes.  `stats["shard"]` receives file_bytes, kept_bytes, skipped_files, groups,
+scratch_bytes and gather_s.
 """
 from __future__ import annotations
 
@@ -27,14 +37,32 @@ import torch
 
 from . import _core, ops
 from . import device as zdev
+from . import shard as zshard
 
 
 def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: bool = True, peers=None,
                    tracker=None, dht: bool = True, dht_bootstrap=None, repo_type: str = "model",
-                   save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False):
+                   save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False,
+                   shard=None, scratch_bytes: int | None = None, stats: dict | None = None):
+    if shard is not None:
+        if device is None:
+            raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu')")
+        if device == "all":
+            raise ValueError("shard= is not supported with device='all': run one process per GPU with "
+                             "device='cuda:N' (a collective sharded pull does not exist yet)")
+        if seed is not False and seed is not None:
+            raise ValueError("shard= is not supported with seed=: the file bytes do not stay resident; seed from "
+                             "an unsharded pull")
+        if save_snapshot:
+            raise ValueError("shard= is not supported with save_snapshot=True: whole files never stay in memory; "
+                             "write the snapshot with a plain pull(repo)")
     dev = torch.device(device)
     if dev.type not in ("cuda", "cpu"):
         raise ValueError("pull_to_device needs a GPU or the CPU")
+    if shard is not None:
+        return _pull_sharded(repo, revision, dev, zshard.as_shard(shard), scratch_bytes, stats, p2p=p2p, peers=peers,
+                             tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap, repo_type=repo_type,
+                             staging_bytes=staging_bytes, threads=threads, include=include)
     seed_port = None
     if seed is not False and seed is not None:
         from .seed import seed_port as _seed_port
@@ -84,6 +112,128 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
             for f in plain:
                 buf = zdev.load_file(os.path.join(r["snapshot_dir"], f["path"]), dev)
                 _add_views(out, buf, f["path"])
+    return out
+
+
+DEFAULT_SCRATCH = 16 << 30  # a default to revisit with measurements, not a tuned value
+
+
+def _slot(size: int) -> int:
+    """Scratch bytes of one file: its size rounded up to ops.PAD plus one more PAD (the decoders
+    write wide, and a staging batch may cross file boundaries)."""
+    return -(-size // ops.PAD) * ops.PAD + ops.PAD
+
+
+def _groups(files, scratch: int):
+    """Files in listing order, cut into groups whose slots fit `scratch`: [(file, slot offset), ...]."""
+    out, cur, pos = [], [], 0
+    for f in files:
+        s = _slot(f["size"])
+        if cur and pos + s > scratch:
+            out.append(cur)
+            cur, pos = [], 0
+        cur.append((f, pos))
+        pos += s
+    if cur:
+        out.append(cur)
+    return out
+
+
+def _pull_sharded(repo, revision, dev, sh, scratch_bytes, stats, *, p2p, peers, tracker, dht, dht_bootstrap, repo_type,
+                  staging_bytes, threads, include):
+    """pull_to_device(shard=...): whole files are pulled and verified (a Xet file hash is a Merkle
+    root over every chunk of the file) into one reused scratch, group by group; after a group
+    verifies, only the rank's slices are copied out (ops.slice_gather) into one compact arena per
+    file, and the scratch is reused.  Bounds device memory, not network bytes."""
+    import time
+
+    net = (p2p, list(peers or []), tracker, dht, list(dht_bootstrap or []))
+    commit, files = _core.list_repo_files(repo, revision, repo_type)
+    has_index = any(f["path"] == zshard.INDEX_NAME for f in files)
+    if include:
+        files = [f for f in files if any(f["path"].endswith(x) for x in include)]
+    st_files = [f for f in files if f["path"].endswith(".safetensors")]
+    skipped: set = set()
+    if has_index and st_files:  # which file holds which tensor, without fetching any of them
+        r = _core.pull(repo, revision, *net, [zshard.INDEX_NAME], True, 0, repo_type)
+        with open(os.path.join(r["snapshot_dir"], zshard.INDEX_NAME), "rb") as fh:
+            skipped = zshard.files_to_skip(fh.read(), [f["path"] for f in st_files], sh)
+        st_files = [f for f in st_files if f["path"] not in skipped]
+    xet = [f for f in st_files if f["xet_hash"]]
+    plain = [f for f in st_files if not f["xet_hash"]]
+    cuda = dev.type == "cuda"
+    out: dict[str, torch.Tensor] = {}
+    info = {"file_bytes": 0, "kept_bytes": 0, "skipped_files": sorted(skipped), "groups": 0, "scratch_bytes": 0,
+            "gather_s": 0.0}
+    timed = []  # cuda: (start, end) events around each group's gathers, read once at the end
+
+    def gather(buf: torch.Tensor, path: str) -> None:
+        """Plan one verified file in `buf`, gather the kept slices into a new arena, add the views."""
+        (hlen,) = struct.unpack("<Q", buf[:8].cpu().numpy().tobytes())
+        start, meta = zdev.parse_safetensors_header(buf[:8 + hlen].cpu().numpy().tobytes())
+        plan = zshard.plan_file(start, meta, sh, buf.numel())
+        arena = ops.padded_empty(plan.arena_bytes, dev) if cuda else torch.empty(plan.arena_bytes, dtype=torch.uint8)
+        ops.slice_gather(buf, plan.table, arena)
+        for k, v in plan.views(arena).items():
+            if k in out:
+                raise ValueError(f"duplicate tensor {k} in {path}")
+            out[k] = v
+        info["file_bytes"] += buf.numel()
+        info["kept_bytes"] += sum(t.nbytes for t in plan.tensors)
+
+    if xet:
+        biggest = max(_slot(f["size"]) for f in xet)
+        want = max(max(f["size"] for f in xet), DEFAULT_SCRATCH) if scratch_bytes is None else int(scratch_bytes)
+        scratch_n = min(max(want, biggest), sum(_slot(f["size"]) for f in xet))  # never more than every file at once
+        groups = _groups(xet, scratch_n)
+        info["groups"], info["scratch_bytes"] = len(groups), scratch_n
+        if cuda:
+            dp = ops.hip().DeviceXetPull(repo, revision, repo_type, *net, dev.index or 0, staging_bytes, threads)
+            with torch.cuda.device(dev):
+                scratch = ops.padded_empty(scratch_n, dev)
+                torch.cuda.synchronize(dev)  # the allocation is visible to the pull's private stream
+                for g in groups:
+                    # one pipeline per group: staging batches cross file boundaries, every file keeps its
+                    # Merkle check and CDN repair pass
+                    dp.pull_files([(f["xet_hash"], scratch.data_ptr() + o, f["size"]) for f, o in g])
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                    for f, o in g:
+                        gather(scratch[o:o + f["size"]], f["path"])
+                    ev1.record()
+                    timed.append((ev0, ev1))
+                    # The next group overwrites the scratch these gathers read.  Only the pipeline's
+                    # compute stream writes caller memory (its H2D copies land in its own staging), so
+                    # queueing that stream behind the gathers' event is enough: no host sync.
+                    dp.order_after(ev1.cuda_event)
+                del scratch  # back to torch's allocator, which orders its reuse behind the gathers' stream
+        else:
+            hf = _core.HostXetFetcher(repo, revision, repo_type, *net, threads)
+            scratch = torch.empty(scratch_n, dtype=torch.uint8)
+            for g in groups:
+                hf.fetch_files([(f["xet_hash"], scratch.data_ptr() + o, f["size"]) for f, o in g])
+                t0 = time.perf_counter()
+                for f, o in g:
+                    gather(scratch[o:o + f["size"]], f["path"])
+                info["gather_s"] += time.perf_counter() - t0
+    if plain:  # non-Xet safetensors: the host route, then the same plan and gather
+        r = _core.pull(repo, revision, *net, [f["path"] for f in plain], True, 0, repo_type)
+        for f in plain:
+            buf = zdev.load_file(os.path.join(r["snapshot_dir"], f["path"]), dev)
+            t0 = time.perf_counter()
+            if cuda:
+                with torch.cuda.device(dev):
+                    gather(buf, f["path"])
+                    torch.cuda.current_stream(dev).synchronize()  # buf is freed before the next file loads
+            else:
+                gather(buf, f["path"])
+            info["gather_s"] += time.perf_counter() - t0
+            del buf
+    if timed:
+        torch.cuda.synchronize(dev)
+        info["gather_s"] += sum(a.elapsed_time(b) for a, b in timed) / 1e3
+    if stats is not None:
+        stats["shard"] = info
     return out
 
 

@@ -6,7 +6,7 @@ bad descriptor can never become an out-of-bounds GPU access.  GPU tensors always
 CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/CPU tests use.
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
-K5 cdc_candidates, K7 pack_chunks, K9 serve_pack.
+K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather.
 """
 from __future__ import annotations
 
@@ -616,6 +616,87 @@ def _serve_pack_cpu(run: ServeRun, lo: int, hi: int) -> np.ndarray:
         out[a - lo:b - lo] = ser[a - s:b - s]
         c += 1
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# K10: gather the kept slices of many tensors out of one file buffer into a compact arena
+# ----------------------------------------------------------------------------------------------
+SLICE_DTYPE = np.dtype([("src_off", "<u8"), ("run_bytes", "<u8"), ("src_stride", "<u8"), ("n_runs", "<u8"),
+                        ("dst_off", "<u8")])
+SLICE_ALIGN = 16  # what the kernel relies on for dst and every dst_off (zest_amd.shard hands out 256)
+
+
+def _check_slice_table(table, src_n: int, dst_n: int) -> tuple[np.ndarray, np.ndarray]:
+    """Validate a slice table against its buffers; returns (table, output bytes per entry)."""
+    table = np.ascontiguousarray(table, dtype=SLICE_DTYPE).reshape(-1)
+    big = lambda f: [int(x) for x in table[f]]  # Python ints: no uint64 wrap-around in the checks
+    so, rb, st, nr, do = (big(f) for f in SLICE_DTYPE.names)
+    size = []
+    end = 0  # end of the outputs so far
+    for i in range(len(table)):
+        n = rb[i] * nr[i]
+        size.append(n)
+        if n and st[i] < rb[i]:
+            raise ValueError(f"slice_gather: entry {i}: src_stride {st[i]} < run_bytes {rb[i]}")
+        if n and so[i] + (nr[i] - 1) * st[i] + rb[i] > src_n:
+            raise ValueError(f"slice_gather: entry {i}: runs reach past the source ({src_n} bytes)")
+        if do[i] % SLICE_ALIGN:
+            raise ValueError(f"slice_gather: entry {i}: dst_off {do[i]} is not {SLICE_ALIGN}-byte aligned")
+        if do[i] + n > dst_n:
+            raise ValueError(f"slice_gather: entry {i}: output reaches past the arena ({dst_n} bytes)")
+        if do[i] < end:
+            raise ValueError(f"slice_gather: entry {i}: dst_off {do[i]} overlaps or precedes the entry before it")
+        end = do[i] + n
+    return table, np.asarray(size, dtype=np.uint64)
+
+
+def slice_gather(src: torch.Tensor, table, dst: torch.Tensor, stream=None) -> None:
+    """Copy the kept slices of many tensors out of `src` (uint8, e.g. a verified safetensors file)
+    into the compact arena `dst` (uint8): K10, csrc/gpu/shard.hip.
+
+    table: SLICE_DTYPE records.  Entry i is n_runs runs of run_bytes bytes, run r read at
+    src_off + r * src_stride, laid end to end at dst_off.  Nothing is checked on the device, so a table
+    is refused here (ValueError naming the entry) unless every run lies inside src, every output
+    lies inside dst, and the outputs are disjoint, ascending and 16-byte aligned.  Zero-size entries
+    are legal.  Only the outputs are written: padding between them keeps its bytes.  GPU tensors: one
+    asynchronous launch on `stream` (default: the current stream); CPU tensors: a NumPy path."""
+    if src.dtype != torch.uint8 or dst.dtype != torch.uint8 or not src.is_contiguous() or not dst.is_contiguous():
+        raise ValueError("slice_gather: src and dst must be contiguous uint8 tensors")
+    if src.device != dst.device:
+        raise ValueError("slice_gather: src and dst must share a device")
+    table, size = _check_slice_table(table, src.numel(), dst.numel())
+    n = len(table)
+    if n == 0 or not size.any():
+        return
+    if src.device.type != "cuda":
+        return _slice_gather_cpu(src.reshape(-1).numpy(), table, dst.reshape(-1).numpy())
+    if dst.data_ptr() % SLICE_ALIGN:
+        raise ValueError(f"slice_gather: dst must be {SLICE_ALIGN}-byte aligned")
+    H = hip()
+    soa = np.empty((H.SLICE_ROWS, n), dtype=np.uint64)
+    for k, f in enumerate(SLICE_DTYPE.names):
+        soa[k] = table[f]
+    soa[5] = table["dst_off"] + size
+    if stream is None:
+        st = _stream(src.device)
+        tab = _dev_array(soa, src.device)
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the table's upload and its free are ordered on the launch's stream
+            tab = _dev_array(soa, src.device)
+    H.slice_gather(src.data_ptr(), tab.data_ptr(), n, int(soa[5, -1]), dst.data_ptr(), st)
+
+
+def _slice_gather_cpu(src: np.ndarray, table: np.ndarray, dst: np.ndarray) -> None:
+    for e in table:
+        so, rb, st, nr, do = (int(e[f]) for f in SLICE_DTYPE.names)
+        if rb == 0 or nr == 0:
+            continue
+        if nr == 1 or st == rb:
+            dst[do:do + rb * nr] = src[so:so + rb * nr]
+            continue
+        runs = np.lib.stride_tricks.as_strided(src[so:], shape=(nr, rb), strides=(st, 1), writeable=False)
+        dst[do:do + rb * nr].reshape(nr, rb)[...] = runs
 
 
 # ----------------------------------------------------------------------------------------------
