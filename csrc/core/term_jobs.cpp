@@ -260,4 +260,65 @@ std::vector<std::pair<uint64_t, uint64_t>> copy_ranges(const std::vector<uint64_
   return out;
 }
 
+PassPlan plan_pass(const std::vector<PassSeg>& segs) {
+  const size_t ns = segs.size();
+  PassPlan p;
+  p.seg_chunk0.assign(ns + 1, 0);
+  p.seg_dst0.assign(ns, 0);
+  if (!ns) return p;
+  uintptr_t base = UINTPTR_MAX, top = 0;
+  for (const PassSeg& sg : segs) {
+    uint64_t bytes = 0;
+    for (const TermShape& t : sg.terms) bytes += t.ulen;
+    base = std::min(base, sg.dst);
+    top = std::max<uintptr_t>(top, sg.dst + bytes);
+  }
+  for (size_t s = 0; s < ns; ++s) {
+    const PassSeg& sg = segs[s];
+    if (sg.chunk0 != segs[0].chunk0 + p.seg_chunk0[s])
+      throw Error("InvalidArgument", "segments must cover consecutive chunks");
+    p.seg_dst0[s] = sg.dst - base;
+    uint64_t off = 0, c = p.seg_chunk0[s];
+    for (size_t i = 0; i < sg.terms.size(); ++i) {
+      const TermShape& t = sg.terms[i];
+      p.terms.push_back({s, sg.t0 + i, p.seg_dst0[s] + off, c, t.nchunks, t.ulen});
+      off += t.ulen;
+      c += t.nchunks;
+    }
+    p.seg_chunk0[s + 1] = c;
+  }
+  p.base = base;
+  p.span = top - base;
+  p.n_chunks = p.seg_chunk0[ns];
+  return p;
+}
+
+std::vector<PlannedBatch> plan_batches(const std::vector<PassTerm>& terms, uint64_t n_chunks, uint64_t first_cap,
+                                       uint64_t cap) {
+  const size_t n = terms.size();
+  std::vector<PlannedBatch> out;
+  for (size_t next = 0; next < n;) {
+    PlannedBatch b;
+    b.begin = next;
+    const uint64_t cap_b = out.empty() ? first_cap : cap;
+    uint64_t pos = 0;
+    size_t end = next;
+    while (end < n) {
+      const uint64_t bound = term_bound(terms[end].ulen, terms[end].nchunks);
+      if (pos + bound > cap_b && end > next) break;
+      b.off.push_back(pos);
+      pos += bound;
+      b.ubytes += terms[end].ulen;
+      b.max_bound = std::max(b.max_bound, bound);
+      ++end;
+    }
+    b.end = end;
+    b.c_lo = terms[next].chunk;
+    b.c_hi = end < n ? terms[end].chunk : n_chunks;
+    out.push_back(std::move(b));
+    next = end;
+  }
+  return out;
+}
+
 }  // namespace zest

@@ -106,4 +106,56 @@ std::vector<TermJobResult> fetch_terms_host(XetBridge& bridge, ReconCache& recs,
 std::vector<std::pair<uint64_t, uint64_t>> copy_ranges(const std::vector<uint64_t>& at,
                                                        const std::vector<uint64_t>& len, uint64_t max_gap);
 
+// Planning of a device pull's pass (csrc/gpurt/device_pull.cpp): pure arithmetic over term shapes,
+// shared by the one-pass and the streaming pipeline.
+
+// Upper bound of a term's fetched bytes: Xet stores a chunk uncompressed when compression does
+// not help, so the payload is <= its unpacked size plus LZ4 frame overhead; + 8-byte headers.
+inline uint64_t term_bound(uint64_t unpacked, uint64_t nchunks) {
+  return unpacked + unpacked / 128 + 80 * nchunks + 4096;
+}
+
+// A contiguous term range of one file: outputs from address `dst`, chunk hashes / sizes at index
+// chunk0.. of the caller's tables; `terms` are the shapes of the file's terms t0, t0 + 1, ...
+struct PassSeg {
+  uintptr_t dst = 0;
+  uint64_t chunk0 = 0;
+  uint32_t t0 = 0;
+  std::vector<TermShape> terms;
+};
+// A term of a pass in segment order: its segment, term index in the file, output offset from the
+// pass's base address, first chunk (pass-relative), chunk count and unpacked size.
+struct PassTerm {
+  size_t seg, term;
+  uint64_t dst;
+  uint64_t chunk;
+  uint32_t nchunks;
+  uint64_t ulen;
+};
+struct PassPlan {
+  std::vector<PassTerm> terms;
+  std::vector<uint64_t> seg_chunk0;  // ns + 1 entries: first pass-relative chunk of each segment
+  std::vector<uint64_t> seg_dst0;    // each segment's output offset from `base`
+  uintptr_t base = 0;                // lowest output address of the pass
+  uint64_t span = 0;                 // bytes from `base` to the highest output end
+  uint64_t n_chunks = 0;
+};
+// Segments must cover consecutive chunk indices (chunk0 of seg k+1 = chunk0 of seg k + its chunks),
+// so a pass's hashes and sizes land in one run from segs[0].chunk0; throws InvalidArgument otherwise.
+PassPlan plan_pass(const std::vector<PassSeg>& segs);
+
+// Consecutive terms [begin, end) that share one staging slot: term begin + j owns the region at
+// `off[j]` of term_bound bytes (a reserved region per term, so a run is received straight into place).
+struct PlannedBatch {
+  size_t begin = 0, end = 0;
+  std::vector<uint64_t> off;
+  uint64_t c_lo = 0, c_hi = 0;  // pass-relative chunk range
+  uint64_t ubytes = 0;          // unpacked bytes of its terms
+  uint64_t max_bound = 0;       // largest term_bound (over `cap`: the slots must grow to it)
+};
+// Packs the terms in order into batches whose bounds fit `cap` bytes (the pass's first batch:
+// `first_cap`); a term that fits no slot forms a batch of its own.
+std::vector<PlannedBatch> plan_batches(const std::vector<PassTerm>& terms, uint64_t n_chunks, uint64_t first_cap,
+                                       uint64_t cap);
+
 }  // namespace zest

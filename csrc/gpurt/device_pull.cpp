@@ -309,15 +309,7 @@ struct DeviceXetPull::Impl {
                                         bool repair) {
     init_device();
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    std::vector<Seg> segs;
-    uint64_t next_chunk = jobs.empty() ? 0 : jobs[0].chunk0;
-    for (const TermJob& j : jobs) {
-      const cas::Reconstruction& rec = sh_->recs->get(j.xet_hash);
-      if (j.t0 > j.t1 || j.t1 > rec.terms.size()) throw Error("RangeOutOfBounds", "term range of " + j.xet_hash);
-      if (j.chunk0 != next_chunk) throw Error("InvalidArgument", "term jobs must cover consecutive chunk indices");
-      for (uint32_t t = j.t0; t < j.t1; ++t) next_chunk += rec.terms[t].range.end - rec.terms[t].range.start;
-      segs.push_back({&rec, j.t0, j.t1, j.dst, j.chunk0});
-    }
+    const std::vector<Seg> segs = segs_of_jobs(jobs);
     std::vector<TermJobResult> out(jobs.size());
     std::vector<size_t> todo(segs.size());
     for (size_t i = 0; i < todo.size(); ++i) todo[i] = i;
@@ -325,8 +317,6 @@ struct DeviceXetPull::Impl {
       FetchOptions opt;
       opt.repair = repair || attempt > 0;
       if (attempt > 0) opt.allow_cache = opt.allow_p2p = false;
-      std::vector<Seg> part;
-      for (size_t i : todo) part.push_back(segs[i]);
       // a retry covers a subset: its chunk indices are no longer consecutive, so run it seg by seg
       std::vector<std::vector<size_t>> groups;
       if (attempt == 0) groups.push_back(todo);
@@ -337,36 +327,17 @@ struct DeviceXetPull::Impl {
         std::vector<Seg> gs;
         for (size_t i : g) gs.push_back(segs[i]);
         SegAttempt at = run_segments(gs, hashes, sizes, opt, attempt, {});
-        auto drop = [&](size_t k) {
-          for (size_t t = 0; t < at.sources[k].size(); ++t)
-            sh_->bridge->settle(gs[k].rec->terms[gs[k].t0 + t].hash_hex, at.sources[k][t].src, at.sources[k][t].run_offset,
-                            at.sources[k][t].pending, false);
-        };
         if (!at.fetch_err.empty()) {
-          // The range is refetched elsewhere: drop the peer runs this call quarantined (never to be
-          // Merkle-checked); cache hits and earlier calls' runs wait for their file's verdict.
-          for (size_t k = 0; k < gs.size(); ++k)
-            for (const TermSource& ts : at.sources[k])
-              if (ts.src == Source::Peer && !ts.pending.empty())
-                sh_->bridge->settle(std::string(), ts.src, ts.run_offset, ts.pending, false);
+          for (size_t k = 0; k < gs.size(); ++k) drop_quarantined(at.sources[k]);
           throw Error("DownloadFailed", at.fetch_err);
         }
         for (size_t k = 0; k < gs.size(); ++k) {
           const size_t i = g[k];
           if (at.ingest_err || !at.planned_ok[k]) {
-            drop(k);
+            drop_runs(gs[k], at.sources[k]);
             bad.push_back(i);
-            continue;
-          }
-          TermJobResult& r = out[i];
-          r.chunk_lens = std::move(at.chunk_lens[k]);
-          r.fetched += at.seg_fetched[k];
-          for (size_t t = 0; t < at.sources[k].size(); ++t) {
-            const TermSource& ts = at.sources[k][t];
-            const cas::Term& term = gs[k].rec->terms[gs[k].t0 + t];
-            sh_->book.add(jobs[i].xet_hash, term.hash_hex, ts.src, ts.run_offset, ts.pending);
-            (ts.src == Source::Peer ? r.from_peer : ts.src == Source::Cache ? r.from_cache : r.from_cdn) +=
-                term.unpacked_length;
+          } else {
+            out[i] = book_seg(jobs[i].xet_hash, gs[k], at, k);
           }
         }
         if (at.ingest_err && attempt > 0)
@@ -414,6 +385,14 @@ struct DeviceXetPull::Impl {
     uint64_t chunk0;
   };
   struct SegAttempt {
+    SegAttempt() = default;
+    SegAttempt(const std::vector<Seg>& segs, const PassPlan& plan)
+        : sources(segs.size()), chunk_lens(segs.size()), planned_ok(segs.size(), 1), seg_fetched(segs.size(), 0) {
+      for (size_t s = 0; s < segs.size(); ++s) {
+        sources[s].resize(segs[s].t1 - segs[s].t0);
+        chunk_lens[s].assign(size_t(plan.seg_chunk0[s + 1] - plan.seg_chunk0[s]), 0);
+      }
+    }
     std::vector<std::vector<TermSource>> sources;   // per seg, per term
     std::vector<std::vector<uint32_t>> chunk_lens;  // per seg: uncompressed chunk sizes
     std::vector<uint8_t> planned_ok;                // per seg: every fetched run matched the plan
@@ -429,29 +408,114 @@ struct DeviceXetPull::Impl {
     std::string fetch_err;
   };
 
-  // A term of a pass in segment order: its segment, term index, output offset from the pass's base
-  // address, first chunk (pass-relative), chunk count and unpacked size.
-  struct GTerm {
-    size_t seg, term;
-    uint64_t dst;
-    uint64_t chunk;
-    uint32_t nchunks;
-    uint64_t ulen;
+  // A planned batch (zest::plan_batches) and what its fetches found, per term.
+  struct Batch : PlannedBatch {
+    explicit Batch(PlannedBatch p)
+        : PlannedBatch(std::move(p)), len(end - begin, 0), src_at(end - begin, 0),
+          hs_bytes(zg_ingest_scratch_bytes(int(c_hi - c_lo), ubytes)) {}
+    std::vector<uint64_t> len, src_at;  // fetched bytes, run start in the slot
+    size_t hs_bytes;                    // scratch of its ingest launch
   };
-  struct TermFetch {
-    uint64_t src_at = 0, len = 0;  // the run's chunk span in the slot: offset, bytes
-    TermSource src;
-    bool planned = true;           // the run matched the term's plan (else its records stay zero)
-  };
-  // One term of a pass: fetch its run through the cache -> P2P -> CDN waterfall into `region` (the
-  // term's reserved part of a pinned staging slot, `room` bytes, at `region_off` in the slot) and
-  // write its chunks' device records into `cr` and their sizes into `lens`.  A run that does not
-  // match the plan keeps zero (no-op) records, so its file fails the Merkle check and takes the
-  // repair path.  `copied` runs once no writer copy thread reads the region any more (now, unless
-  // the fetch deferred the cache copy to the writer).  Throws on a fetch error.
-  TermFetch fetch_term_into(const cas::Reconstruction& rec, const GTerm& g, const FetchOptions& topt,
-                            const std::function<void()>& copied, uint8_t* region, uint64_t room, uint64_t region_off,
-                            uint32_t tag, ZgChunk* cr, uint32_t* lens, TermSource& src_out) {
+
+  // The jobs' term ranges as segments; the jobs must cover consecutive chunk indices.
+  std::vector<Seg> segs_of_jobs(const std::vector<TermJob>& jobs) {
+    std::vector<Seg> segs;
+    uint64_t next_chunk = jobs.empty() ? 0 : jobs[0].chunk0;
+    for (const TermJob& j : jobs) {
+      const cas::Reconstruction& rec = sh_->recs->get(j.xet_hash);
+      if (j.t0 > j.t1 || j.t1 > rec.terms.size()) throw Error("RangeOutOfBounds", "term range of " + j.xet_hash);
+      if (j.chunk0 != next_chunk) throw Error("InvalidArgument", "term jobs must cover consecutive chunk indices");
+      for (uint32_t t = j.t0; t < j.t1; ++t) next_chunk += rec.terms[t].range.end - rec.terms[t].range.start;
+      segs.push_back({&rec, j.t0, j.t1, j.dst, j.chunk0});
+    }
+    return segs;
+  }
+
+  // Layout of a pass over the segments (zest::plan_pass); chunk indices are relative to segs[0].chunk0.
+  static PassPlan plan_segs(const std::vector<Seg>& segs) {
+    std::vector<PassSeg> ps;
+    for (const Seg& sg : segs) {
+      ps.push_back({sg.dst, sg.chunk0, sg.t0, {}});
+      for (uint32_t t = sg.t0; t < sg.t1; ++t)
+        ps.back().terms.push_back({sg.rec->terms[t].unpacked_length,
+                                   uint32_t(sg.rec->terms[t].range.end - sg.rec->terms[t].range.start)});
+    }
+    return plan_pass(ps);
+  }
+
+  // The pass's batches (zest::plan_batches).  One huge term enlarges every slot first, with the
+  // pipeline idle; the batches are then planned for the slots as they are.
+  std::vector<PlannedBatch> plan_slots(const PassPlan& plan, bool first_of_pass) {
+    auto plan_now = [&] {
+      return plan_batches(plan.terms, plan.n_chunks, first_of_pass ? first_batch_cap() : cap_, cap_);
+    };
+    std::vector<PlannedBatch> bs = plan_now();
+    uint64_t max_bound = 0;
+    for (const PlannedBatch& b : bs) max_bound = std::max(max_bound, b.max_bound);
+    if (max_bound > cap_) {
+      s_drain();
+      grow_staging(max_bound);
+      bs = plan_now();
+    }
+    return bs;
+  }
+
+  // Every slot's pinned record table holds `max_recs` chunk records (only with both streams idle).
+  void ensure_record_tables(size_t max_recs) {
+    for (auto& sl : slots_)
+      if (sl.rec_cap < max_recs) {
+        const size_t cap = std::max(max_recs, size_t(16384));
+        if (!sl.rec_pin.alloc(cap * sizeof(ZgChunk))) throw Error("HipError", "pinning the chunk records failed");
+        sl.rec_cap = cap;
+      }
+  }
+
+  // A finished segment's result; the runs behind its terms go to the settle book until the file's
+  // verdict (settle).
+  TermJobResult book_seg(const std::string& file_hex, const Seg& sg, SegAttempt& at, size_t k) {
+    TermJobResult r;
+    r.chunk_lens = std::move(at.chunk_lens[k]);
+    r.fetched = at.seg_fetched[k];
+    for (size_t t = 0; t < at.sources[k].size(); ++t) {
+      const TermSource& ts = at.sources[k][t];
+      const cas::Term& term = sg.rec->terms[sg.t0 + t];
+      sh_->book.add(file_hex, term.hash_hex, ts.src, ts.run_offset, ts.pending);
+      (ts.src == Source::Peer ? r.from_peer : ts.src == Source::Cache ? r.from_cache : r.from_cdn) +=
+          term.unpacked_length;
+    }
+    return r;
+  }
+  // Drop / evict the runs behind every term of a segment that did not decode or match its plan.
+  void drop_runs(const Seg& sg, const std::vector<TermSource>& sources) {
+    for (size_t t = 0; t < sources.size(); ++t)
+      sh_->bridge->settle(sg.rec->terms[sg.t0 + t].hash_hex, sources[t].src, sources[t].run_offset, sources[t].pending,
+                          false);
+  }
+  // A failed call's range is refetched elsewhere: drop the peer runs the call quarantined (never to
+  // be Merkle-checked); cache hits and earlier calls' runs wait for their file's verdict.
+  void drop_quarantined(const std::vector<TermSource>& sources) {
+    for (const TermSource& ts : sources)
+      if (ts.src == Source::Peer && !ts.pending.empty())
+        sh_->bridge->settle(std::string(), ts.src, ts.run_offset, ts.pending, false);
+  }
+
+  // Term i of a pass, in batch `bt` filling slot `s`: fetch its run through the cache -> P2P -> CDN
+  // waterfall into the term's reserved region of the pinned slot (received straight into place when
+  // it fits, no intermediate heap buffer; otherwise only its chunk span is copied in) and write its
+  // chunks' device records into the slot's table, their sizes and the run's source into `at`.
+  // Returns whether the run matched the term's plan: one that does not keeps zero (no-op) records,
+  // so its file fails the Merkle check and takes the repair path.  `copied` runs once no writer copy
+  // thread reads the region any more (now, unless the fetch deferred the cache copy to the writer).
+  // Throws on a fetch error.
+  bool fetch_term_into(const std::vector<Seg>& segs, const PassPlan& plan, SegAttempt& at, Batch& bt, Slot& s, size_t i,
+                       const FetchOptions& topt, const std::function<void()>& copied) {
+    const PassTerm& g = plan.terms[i];
+    const cas::Reconstruction& rec = *segs[g.seg].rec;
+    const size_t j = i - bt.begin;
+    const uint64_t region_off = bt.off[j], room = (i + 1 < bt.end ? bt.off[j + 1] : cap_) - region_off;
+    uint8_t* region = s.host + region_off;
+    ZgChunk* cr = s.recs() + (g.chunk - bt.c_lo);
+    uint32_t* lens = at.chunk_lens[g.seg].data() + (g.chunk - plan.seg_chunk0[g.seg]);
     auto sink = [&](size_t nbytes) -> uint8_t* { return nbytes <= room ? region : nullptr; };
     XorbFetchResult r;
     try {
@@ -461,23 +525,18 @@ struct DeviceXetPull::Impl {
       throw;
     }
     if (!r.copy_deferred) copied();
-    TermFetch tf;
-    tf.src = TermSource{r.source, r.run_offset, r.pending};
-    src_out = tf.src;  // (recorded before any check below throws: a quarantined run is dropped on failure)
+    // (recorded before any check below throws: a quarantined run is dropped on failure)
+    at.sources[g.seg][g.term - segs[g.seg].t0] = TermSource{r.source, r.run_offset, r.pending};
     auto idx = xet::index_chunks(r.bytes(), r.size());
     if (r.local_end > idx.size() || r.local_start >= r.local_end)
       throw Error("RangeOutOfBounds", rec.terms[g.term].hash_hex);
     const uint64_t a = idx[r.local_start].header_off;
     const uint64_t e_end = idx[r.local_end - 1].header_off + xet::kChunkHeaderLen + idx[r.local_end - 1].clen;
-    if (r.ext) {
-      tf.src_at = region_off + a;  // already in place
-    } else {
+    if (!r.ext) {
       if (e_end - a > room) throw Error("TermTooLarge", "term " + std::to_string(g.term) + " exceeds its bound");
       std::memcpy(region, r.data.data() + a, e_end - a);
-      tf.src_at = region_off;
     }
-    tf.len = e_end - a;
-    const uint64_t run0 = tf.src_at;
+    const uint64_t run0 = r.ext ? region_off + a : region_off;  // (ext: received in place)
     uint64_t uoff = 0;
     bool ok = r.local_end - r.local_start == g.nchunks;
     for (uint32_t c = r.local_start; ok && c < r.local_end; ++c) {
@@ -487,15 +546,16 @@ struct DeviceXetPull::Impl {
         ok = false;
         break;
       }
-      cr[c - r.local_start] = ZgChunk{run0 + (e.header_off - a) + xet::kChunkHeaderLen, g.dst + uoff, e.clen, e.ulen, sc, tag};
+      cr[c - r.local_start] =
+          ZgChunk{run0 + (e.header_off - a) + xet::kChunkHeaderLen, g.dst + uoff, e.clen, e.ulen, sc, uint32_t(j)};
       lens[c - r.local_start] = e.ulen;
       uoff += e.ulen;
     }
-    if (!ok || uoff != g.ulen) {
-      std::fill(cr, cr + g.nchunks, ZgChunk{});
-      tf.planned = false;
-    }
-    return tf;
+    ok = ok && uoff == g.ulen;
+    if (!ok) std::fill(cr, cr + g.nchunks, ZgChunk{});
+    bt.src_at[j] = run0;
+    bt.len[j] = e_end - a;
+    return ok;
   }
 
   // Publish (ok) or drop/evict (!ok) the cache runs behind every term of the attempt's files.
@@ -570,6 +630,57 @@ struct DeviceXetPull::Impl {
     return at;
   }
 
+  struct Queued {
+    uint64_t fetched, top, h2d;  // the batch's run bytes, the end of its last run in the slot, bytes copied
+  };
+  // Queue a fetched batch on the GPU without waiting for it: the H2D copies of its runs and chunk
+  // records out of slot `s` on the copy stream (after `wait`, the kernels that last read the slot's
+  // device side; may be null), then its decode/place/hash kernels on the compute stream.  `copied`
+  // is recorded behind the copies and `kernels` behind the kernels; `tev` (may be null) are four
+  // timed events: copy start / end, kernels start / end.  Chunks go to [dst, dst + dst_size), their
+  // hashes and sizes to hash_out / size_out (the batch's first chunk), decode errors to `err`.  The
+  // slot's chunks_dev and scratch must already hold the batch.
+  Queued queue_batch(Slot& s, const Batch& bt, uint8_t* dst, uint64_t dst_size, unsigned long long* err,
+                     uint8_t* hash_out, uint64_t* size_out, hipEvent_t wait, hipEvent_t copied, hipEvent_t kernels,
+                     const hipEvent_t* tev) {
+    Queued q{0, 0, 0};
+    for (size_t j = 0; j < bt.len.size(); ++j) {
+      q.fetched += bt.len[j];
+      q.top = std::max<uint64_t>(q.top, bt.src_at[j] + bt.len[j]);
+    }
+    const int nchunks = int(bt.c_hi - bt.c_lo);
+    bool compressed = false;
+    for (int c = 0; c < nchunks && !compressed; ++c) compressed = s.recs()[c].scheme != 0;
+    if (wait) hip_check(hipStreamWaitEvent(copy_stream_, wait, 0), "hipStreamWaitEvent");
+    if (tev) hip_check(hipEventRecord(tev[0], copy_stream_), "event");
+    // Only the fetched runs cross PCIe, to the same offsets (the chunk records address the slot):
+    // each term owns a region sized for its worst case (term_bound), and a compressed run fills
+    // ~88 % of it on bf16 weights.  Neighbours merge across gaps of at most 64 KiB
+    // (ZEST_H2D_MERGE_GAP): small terms share a copy, while a 64 MiB term's ~0.6 MB of worst-case
+    // slack stays off PCIe (docs/ARCHITECTURE.md 15.3 has the figures).
+    static const uint64_t merge_gap = env_size("ZEST_H2D_MERGE_GAP", size_t(64) << 10);
+    for (const auto& [lo, hi] : copy_ranges(bt.src_at, bt.len, merge_gap)) {
+      hip_check(hipMemcpyAsync(s.dev.p + lo, s.host + lo, hi - lo, hipMemcpyHostToDevice, copy_stream_), "H2D");
+      q.h2d += hi - lo;
+    }
+    if (nchunks)
+      hip_check(hipMemcpyAsync(s.chunks_dev.p, s.recs(), sizeof(ZgChunk) * size_t(nchunks), hipMemcpyHostToDevice,
+                               copy_stream_),
+                "H2D chunk records");
+    hip_check(hipEventRecord(copied, copy_stream_), "event");
+    if (tev) hip_check(hipEventRecord(tev[1], copy_stream_), "event");
+    hip_check(hipStreamWaitEvent(stream_, copied, 0), "hipStreamWaitEvent");
+    if (tev) hip_check(hipEventRecord(tev[2], stream_), "event");
+    // decode (when the batch has compressed chunks) + one fused pass placing raw chunks and
+    // hashing every chunk (csrc/gpu/blake3_flat.hip PlaceSrc)
+    hip_check(zg_ingest_chunks(s.dev.p, q.top, dst, dst_size, s.chunks_dev.p, nchunks, compressed ? 1 : 0, err,
+                               hash_out, size_out, 0, s.scratch.p, bt.hs_bytes, stream_),
+              "ingest");
+    hip_check(hipEventRecord(kernels, stream_), "event");
+    if (tev) hip_check(hipEventRecord(tev[3], stream_), "event");
+    return q;
+  }
+
   // One pass over segments: fetch (+ chunk records) -> staging -> H2D -> place/hash.  Segments must
   // cover consecutive chunk indices (chunk0 of seg k+1 = chunk0 of seg k + its chunks): hashes and
   // sizes of the pass go to hashes[segs[0].chunk0 ..] in one run.
@@ -577,93 +688,33 @@ struct DeviceXetPull::Impl {
                           int attempt, const std::function<void(size_t, uint64_t)>& progress) {
     (void)attempt;
     s_drain();  // the streaming engine shares the slots and streams: nothing of it may be in flight
-    const size_t ns = segs.size();
-    SegAttempt at;
-    at.sources.resize(ns);
-    at.chunk_lens.resize(ns);
-    at.planned_ok.assign(ns, 1);
-    at.seg_fetched.assign(ns, 0);
-    // Global term list in segment order; chunk indices are relative to segs[0].chunk0.
-    std::vector<GTerm> gt;
-    std::vector<uint64_t> seg_chunk0(ns + 1, 0), seg_dst0(ns, 0);
-    uintptr_t base = UINTPTR_MAX, top_addr = 0;
-    const uint64_t hash_base = ns ? segs[0].chunk0 : 0;
-    for (size_t s = 0; s < ns; ++s) {
-      uint64_t bytes = 0;
-      for (uint32_t t = segs[s].t0; t < segs[s].t1; ++t) bytes += segs[s].rec->terms[t].unpacked_length;
-      base = std::min(base, segs[s].dst);
-      top_addr = std::max<uintptr_t>(top_addr, segs[s].dst + bytes);
-    }
-    for (size_t s = 0; s < ns; ++s) {
-      const Seg& sg = segs[s];
-      if (sg.chunk0 != hash_base + seg_chunk0[s]) throw Error("InvalidArgument", "segments must cover consecutive chunks");
-      at.sources[s].resize(sg.t1 - sg.t0);
-      seg_dst0[s] = sg.dst - base;
-      uint64_t off = 0, c = seg_chunk0[s];
-      for (uint32_t i = sg.t0; i < sg.t1; ++i) {
-        const auto& t = sg.rec->terms[i];
-        const uint32_t n = uint32_t(t.range.end - t.range.start);
-        gt.push_back({s, i, sg.dst - base + off, c, n, t.unpacked_length});
-        off += t.unpacked_length;
-        c += n;
-      }
-      seg_chunk0[s + 1] = c;
-      at.chunk_lens[s].assign(size_t(c - seg_chunk0[s]), 0);
-    }
-    const uint64_t nck = seg_chunk0[ns];
+    const PassPlan plan = plan_segs(segs);
+    SegAttempt at(segs, plan);
+    const std::vector<PassTerm>& gt = plan.terms;
+    const uint64_t hash_base = segs.empty() ? 0 : segs[0].chunk0;
     const size_t n = gt.size();
-    uint8_t* dst = ns ? reinterpret_cast<uint8_t*>(base) : nullptr;
-    const uint64_t dst_size = ns ? uint64_t(top_addr - base) : 0;
+    uint8_t* dst = reinterpret_cast<uint8_t*>(plan.base);
     hip_check(hipMemsetAsync(err_.p, 0, sizeof(unsigned long long), stream_), "hipMemset");
     std::string& fetch_err = at.fetch_err;
     {
       // Batches: consecutive terms whose fetched-size bounds fit one staging slot, so every term
       // has a reserved region of the pinned buffer (no refetch, no second copy pass: workers
-      // receive / copy their run straight into place).  Batch b fills slot b % slots.
-      uint64_t max_bound = 0;
-      for (size_t i = 0; i < n; ++i) max_bound = std::max(max_bound, term_bound(gt[i].ulen, gt[i].nchunks));
-      if (max_bound > cap_) grow_staging(max_bound);  // one huge term: enlarge every slot
-      struct Batch {
-        size_t begin = 0, end = 0;
-        std::vector<uint64_t> off, len, src_at;  // per term: region, fetched bytes, run start
-      };
+      // receive / copy their run straight into place).  Batch b fills slot b % slots.  The pass's
+      // first batch is small (ZEST_FIRST_BATCH_MB, 128): nothing overlaps its fetch, so the copy
+      // engine starts after ~128 MiB has arrived instead of a whole slot.
       std::vector<Batch> batches;
-      std::vector<uint32_t> batch_of(n);
-      for (size_t next = 0; next < n;) {
-        Batch bt;
-        bt.begin = next;
-        uint64_t pos = 0;
-        size_t end = next;
-        // the pass's first batch is small (ZEST_FIRST_BATCH_MB, 128): nothing overlaps its fetch, so
-        // the copy engine starts after ~128 MiB has arrived instead of a whole slot
-        const uint64_t cap_b = batches.empty() ? first_batch_cap() : cap_;
-        while (end < n) {
-          const uint64_t bound = term_bound(gt[end].ulen, gt[end].nchunks);
-          if (pos + bound > cap_b && end > next) break;
-          bt.off.push_back(pos);
-          pos += bound;
-          batch_of[end++] = uint32_t(batches.size());
-        }
-        bt.end = end;
-        bt.len.assign(end - next, 0);
-        bt.src_at.assign(end - next, 0);
-        batches.push_back(std::move(bt));
-        next = end;
-      }
+      for (PlannedBatch& pb : plan_slots(plan, true)) batches.emplace_back(std::move(pb));
       const size_t nb = batches.size();
       const size_t S = nslots_;
-      auto chunk_lo = [&](size_t b) { return gt[batches[b].begin].chunk; };
-      auto chunk_hi = [&](size_t b) { return batches[b].end < n ? gt[batches[b].end].chunk : nck; };
+      std::vector<uint32_t> batch_of(n);
       // every slot's pinned record table holds the largest batch (the streams are idle here: the
       // previous pass synchronized them)
       size_t max_recs = 1;
-      for (size_t b = 0; b < nb; ++b) max_recs = std::max<size_t>(max_recs, size_t(chunk_hi(b) - chunk_lo(b)));
-      for (auto& sl : slots_)
-        if (sl.rec_cap < max_recs) {
-          const size_t cap = std::max(max_recs, size_t(16384));
-          if (!sl.rec_pin.alloc(cap * sizeof(ZgChunk))) throw Error("HipError", "pinning the chunk records failed");
-          sl.rec_cap = cap;
-        }
+      for (size_t b = 0; b < nb; ++b) {
+        std::fill(batch_of.begin() + long(batches[b].begin), batch_of.begin() + long(batches[b].end), uint32_t(b));
+        max_recs = std::max<size_t>(max_recs, size_t(batches[b].c_hi - batches[b].c_lo));
+      }
+      ensure_record_tables(max_recs);
       hipEvent_t* ev = take_events(2 * nb);  // ev[2b]: batch b's copies landed; ev[2b+1]: its kernels ran
       // ZEST_DEVICE_TIMING=1: timed events around every batch's copy and kernels (device timeline
       // of the pass: copy / kernel busy time and how much of it overlapped, timeline_json())
@@ -705,19 +756,12 @@ struct DeviceXetPull::Impl {
           if (i >= n) return;
           const size_t b = batch_of[i];
           Batch& bt = batches[b];
-          Slot& s = slots_[b % S];
           {
             std::unique_lock<std::mutex> g(mu);
             cv.wait(g, [&] { return abort || ready[b % S] >= b; });
             if (abort) return;
           }
-          const size_t j = i - bt.begin;
           try {
-            const cas::Reconstruction& rec = *segs[gt[i].seg].rec;
-            // The run is received straight into this term's region of the pinned buffer when it
-            // fits (no intermediate heap buffer); otherwise only its chunk span is copied in.
-            uint8_t* region = s.host + bt.off[j];
-            const uint64_t room = (i + 1 < bt.end ? bt.off[j + 1] : cap_) - bt.off[j];
             FetchOptions topt = opt;
             {
               std::lock_guard<std::mutex> g(mu);
@@ -731,13 +775,7 @@ struct DeviceXetPull::Impl {
               cv.notify_all();
             };
             if (sh_->writer) topt.on_copied = copied;
-            ZgChunk* cr = s.recs() + (gt[i].chunk - chunk_lo(b));
-            uint32_t* lens = at.chunk_lens[gt[i].seg].data() + (gt[i].chunk - seg_chunk0[gt[i].seg]);
-            const TermFetch tf = fetch_term_into(rec, gt[i], topt, copied, region, room, bt.off[j], uint32_t(j), cr, lens,
-                                                 at.sources[gt[i].seg][gt[i].term - segs[gt[i].seg].t0]);
-            bt.src_at[j] = tf.src_at;
-            bt.len[j] = tf.len;
-            if (!tf.planned) {
+            if (!fetch_term_into(segs, plan, at, bt, slots_[b % S], i, topt, copied)) {
               std::lock_guard<std::mutex> g(mu);
               at.planned_ok[gt[i].seg] = 0;
             }
@@ -782,7 +820,7 @@ struct DeviceXetPull::Impl {
             const Batch& bt = batches[b];
             for (size_t i = bt.begin; i < bt.end; ++i)
               if (i + 1 == bt.end || gt[i + 1].seg != gt[i].seg)
-                progress(gt[i].seg, gt[i].dst + gt[i].ulen - seg_dst0[gt[i].seg]);
+                progress(gt[i].seg, gt[i].dst + gt[i].ulen - plan.seg_dst0[gt[i].seg]);
           }
         }
       };
@@ -808,62 +846,21 @@ struct DeviceXetPull::Impl {
           }
           const Batch& bt = batches[b];
           Slot& s = slots_[b % S];
-          uint64_t top = 0;
-          for (size_t j = 0; j < bt.len.size(); ++j) {
-            at.fetched += bt.len[j];
-            at.seg_fetched[gt[bt.begin + j].seg] += bt.len[j];
-            top = std::max<uint64_t>(top, bt.src_at[j] + bt.len[j]);
-          }
-          const uint64_t c0 = chunk_lo(b);
-          const int nchunks = int(chunk_hi(b) - c0);
-          uint64_t ubytes = 0;
-          for (size_t i = bt.begin; i < bt.end; ++i) ubytes += gt[i].ulen;
-          bool compressed = false;
-          for (int c = 0; c < nchunks && !compressed; ++c) compressed = s.recs()[c].scheme != 0;
-          const size_t hs_bytes = zg_ingest_scratch_bytes(nchunks, ubytes);
+          for (size_t j = 0; j < bt.len.size(); ++j) at.seg_fetched[gt[bt.begin + j].seg] += bt.len[j];
+          const size_t nrecs = std::max<size_t>(1, size_t(bt.c_hi - bt.c_lo));
           // the slot's device staging, records and scratch are read by batch b - S's kernels
-          if (b >= S && (s.chunks_dev.n < size_t(nchunks ? nchunks : 1) || s.scratch.n < hs_bytes))
-            hip_check(gpu::idle_event_sync(ev[2 * (b - S) + 1]), "hipEventSynchronize");  // growing: wait, then free
-          s.chunks_dev.ensure(size_t(nchunks ? nchunks : 1));
-          s.scratch.ensure(hs_bytes);
+          hipEvent_t prev = b >= S ? ev[2 * (b - S) + 1] : nullptr;
+          if (prev && (s.chunks_dev.n < nrecs || s.scratch.n < bt.hs_bytes))
+            hip_check(gpu::idle_event_sync(prev), "hipEventSynchronize");  // growing: wait, then free
+          s.chunks_dev.ensure(nrecs);
+          s.scratch.ensure(bt.hs_bytes);
           trace::Span submit_span("device", "queue H2D + place/hash");
-          submit_span.arg("\"terms\":" + std::to_string(bt.end - bt.begin) + ",\"bytes\":" + std::to_string(top));
-          if (b >= S) hip_check(hipStreamWaitEvent(copy_stream_, ev[2 * (b - S) + 1], 0), "hipStreamWaitEvent");
-          if (tev) hip_check(hipEventRecord(tev[4 * b], copy_stream_), "event");
-          // Only the fetched bytes cross PCIe: each term owns a region sized for its worst case
-          // (term_bound: every chunk stored raw), and a compressed run fills ~88 % of it on bf16
-          // weights, so one copy of [0, top) moved the holes too (70B bf16 public path: 141 GB over
-          // PCIe for 123.6 GB of runs, 55.2 GB/s against the engine's 64.3).  Runs are copied to
-          // the same offsets (the chunk records address the slot).
-          // (ZEST_H2D_WHOLE_SPAN=1: the old single copy of [0, top), for A/B runs)
-          static const bool whole_span = env_size("ZEST_H2D_WHOLE_SPAN", 0) != 0;
-          // Neighbours merge across gaps of at most 64 KiB (ZEST_H2D_MERGE_GAP): small terms share a
-          // copy, while a 64 MiB term's ~0.6 MB of worst-case slack stays off PCIe -- with 1 MiB
-          // the random-bytes 70B pull moved 142.3 GB for 141.1 (public path 54.2 vs 54.8 GB/s with
-          // no merging, same box; the per-term copies cost nothing visible: 56.3 GB/s busy).
-          static const uint64_t merge_gap = env_size("ZEST_H2D_MERGE_GAP", size_t(64) << 10);
-          const auto ranges = whole_span ? std::vector<std::pair<uint64_t, uint64_t>>{{0, top}}
-                                         : copy_ranges(bt.src_at, bt.len, merge_gap);
-          for (const auto& [lo, hi] : ranges) {
-            hip_check(hipMemcpyAsync(s.dev.p + lo, s.host + lo, hi - lo, hipMemcpyHostToDevice, copy_stream_), "H2D");
-            h2d_bytes += hi - lo;
-          }
-          if (nchunks)
-            hip_check(hipMemcpyAsync(s.chunks_dev.p, s.recs(), sizeof(ZgChunk) * size_t(nchunks), hipMemcpyHostToDevice,
-                                     copy_stream_),
-                      "H2D chunk records");
-          hip_check(hipEventRecord(ev[2 * b], copy_stream_), "event");
-          if (tev) hip_check(hipEventRecord(tev[4 * b + 1], copy_stream_), "event");
-          hip_check(hipStreamWaitEvent(stream_, ev[2 * b], 0), "hipStreamWaitEvent");
-          if (tev) hip_check(hipEventRecord(tev[4 * b + 2], stream_), "event");
-          // decode (when the batch has compressed chunks) + one fused pass placing raw chunks and
-          // hashing every chunk (csrc/gpu/blake3_flat.hip PlaceSrc)
-          hip_check(zg_ingest_chunks(s.dev.p, top, dst, dst_size, s.chunks_dev.p, nchunks, compressed ? 1 : 0, err_.p,
-                                     hash_out + 32 * (hash_base + c0), size_out ? size_out + hash_base + c0 : nullptr, 0,
-                                     s.scratch.p, hs_bytes, stream_),
-                    "ingest");
-          hip_check(hipEventRecord(ev[2 * b + 1], stream_), "event");
-          if (tev) hip_check(hipEventRecord(tev[4 * b + 3], stream_), "event");
+          const Queued q = queue_batch(s, bt, dst, plan.span, err_.p, hash_out + 32 * (hash_base + bt.c_lo),
+                                       size_out ? size_out + hash_base + bt.c_lo : nullptr, prev, ev[2 * b],
+                                       ev[2 * b + 1], tev ? tev + 4 * b : nullptr);
+          submit_span.arg("\"terms\":" + std::to_string(bt.end - bt.begin) + ",\"bytes\":" + std::to_string(q.top));
+          at.fetched += q.fetched;
+          h2d_bytes += q.h2d;
           {
             std::lock_guard<std::mutex> g(mu);
             issued.push_back(b);
@@ -913,10 +910,7 @@ struct DeviceXetPull::Impl {
     uint64_t ticket = 0;
     std::vector<TermJob> jobs;
     std::vector<Seg> segs;
-    std::vector<GTerm> gt;
-    std::vector<uint64_t> seg_chunk0;
-    uint8_t* dst = nullptr;  // base device address (the item's lowest output byte)
-    uint64_t dst_size = 0;
+    PassPlan plan;  // terms, chunk layout and output span of the item
     uint8_t* hash_out = nullptr;  // hashes + 32 * chunk0 of the item
     uint64_t* size_out = nullptr;
     SegAttempt at;
@@ -928,12 +922,10 @@ struct DeviceXetPull::Impl {
     hipEvent_t done = nullptr;
     size_t eslot = 0;        // error word index
   };
-  struct SBatch {
-    SItem* item = nullptr;
-    size_t begin = 0, end = 0;  // terms [begin, end) of item->gt
-    std::vector<uint64_t> off, len, src_at;
-    uint64_t c_lo = 0, c_hi = 0;  // item-relative chunk range
-    size_t remaining = 0;
+  struct SBatch : Batch {  // terms [begin, end) of item->plan; item-relative chunk range
+    SBatch(PlannedBatch p, SItem* it) : Batch(std::move(p)), item(it), remaining(end - begin) {}
+    SItem* item;
+    size_t remaining;
     size_t copies = 0;
     bool gpu = false;  // its H2D + kernels were queued
     uint64_t h2d = 0;  // bytes copied
@@ -1049,102 +1041,31 @@ struct DeviceXetPull::Impl {
     auto item = std::make_unique<SItem>();
     SItem& it = *item;
     it.jobs = jobs;
-    uint64_t next_chunk = jobs.empty() ? 0 : jobs[0].chunk0;
-    for (const TermJob& j : jobs) {
-      const cas::Reconstruction& rec = sh_->recs->get(j.xet_hash);
-      if (j.t0 > j.t1 || j.t1 > rec.terms.size()) throw Error("RangeOutOfBounds", "term range of " + j.xet_hash);
-      if (j.chunk0 != next_chunk) throw Error("InvalidArgument", "term jobs must cover consecutive chunk indices");
-      for (uint32_t t = j.t0; t < j.t1; ++t) next_chunk += rec.terms[t].range.end - rec.terms[t].range.start;
-      it.segs.push_back({&rec, j.t0, j.t1, j.dst, j.chunk0});
-    }
-    const size_t ns = it.segs.size();
-    it.at.sources.resize(ns);
-    it.at.chunk_lens.resize(ns);
-    it.at.planned_ok.assign(ns, 1);
-    it.at.seg_fetched.assign(ns, 0);
-    uintptr_t base = UINTPTR_MAX, top_addr = 0;
-    for (const Seg& sg : it.segs) {
-      uint64_t bytes = 0;
-      for (uint32_t t = sg.t0; t < sg.t1; ++t) bytes += sg.rec->terms[t].unpacked_length;
-      base = std::min(base, sg.dst);
-      top_addr = std::max<uintptr_t>(top_addr, sg.dst + bytes);
-    }
-    it.seg_chunk0.assign(ns + 1, 0);
-    for (size_t sidx = 0; sidx < ns; ++sidx) {
-      const Seg& sg = it.segs[sidx];
-      it.at.sources[sidx].resize(sg.t1 - sg.t0);
-      uint64_t off = 0, c = it.seg_chunk0[sidx];
-      for (uint32_t i = sg.t0; i < sg.t1; ++i) {
-        const auto& t = sg.rec->terms[i];
-        const uint32_t n = uint32_t(t.range.end - t.range.start);
-        it.gt.push_back({sidx, i, sg.dst - base + off, c, n, t.unpacked_length});
-        off += t.unpacked_length;
-        c += n;
-      }
-      it.seg_chunk0[sidx + 1] = c;
-      it.at.chunk_lens[sidx].assign(size_t(c - it.seg_chunk0[sidx]), 0);
-    }
-    const size_t n = it.gt.size();
-    const uint64_t nck = it.seg_chunk0[ns];
-    it.dst = ns ? reinterpret_cast<uint8_t*>(base) : nullptr;
-    it.dst_size = ns ? uint64_t(top_addr - base) : 0;
-    it.hash_out = hashes + 32 * (ns ? it.segs[0].chunk0 : 0);
-    it.size_out = sizes ? sizes + (ns ? it.segs[0].chunk0 : 0) : nullptr;
-    // batches of whole terms that fit a slot (as in run_segments); a term larger than a slot grows
-    // every slot, and the slots' record tables / device buffers grow to the largest batch -- both
-    // only with the pipeline idle
-    uint64_t max_bound = 0;
-    for (size_t i = 0; i < n; ++i) max_bound = std::max(max_bound, term_bound(it.gt[i].ulen, it.gt[i].nchunks));
-    if (max_bound > cap_) {
-      s_drain();
-      grow_staging(max_bound);
-    }
-    std::vector<SBatch> bs;
+    it.segs = segs_of_jobs(jobs);
+    it.plan = plan_segs(it.segs);
+    it.at = SegAttempt(it.segs, it.plan);
+    const uint64_t chunk0 = it.segs.empty() ? 0 : it.segs[0].chunk0;
+    it.hash_out = hashes + 32 * chunk0;
+    it.size_out = sizes ? sizes + chunk0 : nullptr;
     bool first_of_pass;
     {
       std::lock_guard<std::mutex> g(smu_);
       first_of_pass = sbatch_total_ == sb0_;  // nothing submitted since the last reset
     }
-    for (size_t next = 0; next < n;) {
-      SBatch bt;
-      bt.item = &it;
-      bt.begin = next;
-      uint64_t pos = 0;
-      size_t end = next;
-      const uint64_t cap_b = first_of_pass && bs.empty() ? first_batch_cap() : cap_;
-      while (end < n) {
-        const uint64_t bound = term_bound(it.gt[end].ulen, it.gt[end].nchunks);
-        if (pos + bound > cap_b && end > next) break;
-        bt.off.push_back(pos);
-        pos += bound;
-        ++end;
-      }
-      bt.end = end;
-      bt.len.assign(end - next, 0);
-      bt.src_at.assign(end - next, 0);
-      bt.c_lo = it.gt[next].chunk;
-      bt.c_hi = end < n ? it.gt[end].chunk : nck;
-      bt.remaining = end - next;
-      bs.push_back(std::move(bt));
-      next = end;
-    }
+    // the slots' record tables / device buffers grow to the largest batch, only with the pipeline idle
+    std::vector<SBatch> bs;
     size_t max_recs = 1, max_hs = 1;
-    for (const SBatch& bt : bs) {
-      uint64_t ub = 0;
-      for (size_t i = bt.begin; i < bt.end; ++i) ub += it.gt[i].ulen;
-      max_recs = std::max<size_t>(max_recs, size_t(bt.c_hi - bt.c_lo));
-      max_hs = std::max(max_hs, zg_ingest_scratch_bytes(int(bt.c_hi - bt.c_lo), ub));
+    for (PlannedBatch& pb : plan_slots(it.plan, first_of_pass)) {
+      max_recs = std::max<size_t>(max_recs, size_t(pb.c_hi - pb.c_lo));
+      bs.emplace_back(std::move(pb), &it);
+      max_hs = std::max(max_hs, bs.back().hs_bytes);
     }
     bool grow = false;
     for (const auto& sl : slots_) grow |= sl.rec_cap < max_recs || sl.chunks_dev.n < max_recs || sl.scratch.n < max_hs;
     if (grow) {
       s_drain();
+      ensure_record_tables(max_recs);
       for (auto& sl : slots_) {
-        if (sl.rec_cap < max_recs) {
-          const size_t cap = std::max(max_recs, size_t(16384));
-          if (!sl.rec_pin.alloc(cap * sizeof(ZgChunk))) throw Error("HipError", "pinning the chunk records failed");
-          sl.rec_cap = cap;
-        }
         sl.chunks_dev.ensure(std::max(max_recs, sl.rec_cap));
         sl.scratch.ensure(max_hs);
       }
@@ -1215,13 +1136,7 @@ struct DeviceXetPull::Impl {
       }
       SBatch& bt = *bp;
       SItem& it = *bt.item;
-      Slot& s = slots_[g % S];
-      const size_t j = i - bt.begin;
       try {
-        const GTerm& gti = it.gt[i];
-        const cas::Reconstruction& rec = *it.segs[gti.seg].rec;
-        uint8_t* region = s.host + bt.off[j];
-        const uint64_t room = (i + 1 < bt.end ? bt.off[j + 1] : cap_) - bt.off[j];
         FetchOptions topt;
         auto copied = [this, bp]() {
           {
@@ -1231,18 +1146,14 @@ struct DeviceXetPull::Impl {
           scv_.notify_all();
         };
         if (sh_->writer) topt.on_copied = copied;
-        ZgChunk* cr = s.recs() + (gti.chunk - bt.c_lo);
-        uint32_t* lens = it.at.chunk_lens[gti.seg].data() + (gti.chunk - it.seg_chunk0[gti.seg]);
-        const TermFetch tf = fetch_term_into(rec, gti, topt, copied, region, room, bt.off[j], uint32_t(j), cr, lens,
-                                             it.at.sources[gti.seg][gti.term - it.segs[gti.seg].t0]);
-        bt.src_at[j] = tf.src_at;
-        bt.len[j] = tf.len;
+        const bool planned = fetch_term_into(it.segs, it.plan, it.at, bt, slots_[g % S], i, topt, copied);
         std::lock_guard<std::mutex> lk(smu_);
-        if (!tf.planned) {
-          it.at.planned_ok[gti.seg] = 0;
+        if (!planned) {
+          const size_t seg = it.plan.terms[i].seg;
+          it.at.planned_ok[seg] = 0;
           if (!it.failed) {
             it.failed = true;
-            it.err = "term range of " + it.jobs[gti.seg].xet_hash + " does not match its plan";
+            it.err = "term range of " + it.jobs[seg].xet_hash + " does not match its plan";
           }
         }
         if (--bt.remaining == 0) scv_.notify_all();
@@ -1288,42 +1199,16 @@ struct DeviceXetPull::Impl {
         trace::Span sp("device", "stream: queue H2D + place/hash");
         if (first) hip_check(hipMemsetAsync(serr_.p + it.eslot, 0, sizeof(unsigned long long), stream_), "hipMemset");
         if (!failed) {
-          uint64_t top = 0, fetched = 0;
-          for (size_t j = 0; j < bt.len.size(); ++j) {
-            top = std::max<uint64_t>(top, bt.src_at[j] + bt.len[j]);
-            fetched += bt.len[j];
-            it.at.seg_fetched[it.gt[bt.begin + j].seg] += bt.len[j];
-          }
-          it.at.fetched += fetched;
-          const int nchunks = int(bt.c_hi - bt.c_lo);
-          uint64_t ubytes = 0;
-          for (size_t i = bt.begin; i < bt.end; ++i) ubytes += it.gt[i].ulen;
-          bool compressed = false;
-          for (int c = 0; c < nchunks && !compressed; ++c) compressed = s.recs()[c].scheme != 0;
-          const size_t hs_bytes = zg_ingest_scratch_bytes(nchunks, ubytes);
-          if (skern_set_[slot]) hip_check(hipStreamWaitEvent(copy_stream_, skern_[slot], 0), "hipStreamWaitEvent");
+          for (size_t j = 0; j < bt.len.size(); ++j) it.at.seg_fetched[it.plan.terms[bt.begin + j].seg] += bt.len[j];
           if (timing_)
             for (auto& e : bt.tev) hip_check(hipEventCreate(&e), "hipEventCreate");
-          if (timing_) hip_check(hipEventRecord(bt.tev[0], copy_stream_), "event");
-          static const uint64_t merge_gap = env_size("ZEST_H2D_MERGE_GAP", size_t(64) << 10);
-          for (const auto& [lo, hi] : copy_ranges(bt.src_at, bt.len, merge_gap)) {
-            hip_check(hipMemcpyAsync(s.dev.p + lo, s.host + lo, hi - lo, hipMemcpyHostToDevice, copy_stream_), "H2D");
-            bt.h2d += hi - lo;
-          }
-          if (nchunks)
-            hip_check(hipMemcpyAsync(s.chunks_dev.p, s.recs(), sizeof(ZgChunk) * size_t(nchunks), hipMemcpyHostToDevice,
-                                     copy_stream_),
-                      "H2D chunk records");
-          hip_check(hipEventRecord(sh2d_[slot], copy_stream_), "event");
-          if (timing_) hip_check(hipEventRecord(bt.tev[1], copy_stream_), "event");
-          hip_check(hipStreamWaitEvent(stream_, sh2d_[slot], 0), "hipStreamWaitEvent");
-          if (timing_) hip_check(hipEventRecord(bt.tev[2], stream_), "event");
-          hip_check(zg_ingest_chunks(s.dev.p, top, it.dst, it.dst_size, s.chunks_dev.p, nchunks, compressed ? 1 : 0,
-                                     serr_.p + it.eslot, it.hash_out + 32 * bt.c_lo,
-                                     it.size_out ? it.size_out + bt.c_lo : nullptr, 0, s.scratch.p, hs_bytes, stream_),
-                    "ingest");
-          if (timing_) hip_check(hipEventRecord(bt.tev[3], stream_), "event");
-          hip_check(hipEventRecord(skern_[slot], stream_), "event");
+          const Queued q = queue_batch(s, bt, reinterpret_cast<uint8_t*>(it.plan.base), it.plan.span,
+                                       serr_.p + it.eslot, it.hash_out + 32 * bt.c_lo,
+                                       it.size_out ? it.size_out + bt.c_lo : nullptr,
+                                       skern_set_[slot] ? skern_[slot] : nullptr, sh2d_[slot], skern_[slot],
+                                       timing_ ? bt.tev.data() : nullptr);
+          it.at.fetched += q.fetched;
+          bt.h2d = q.h2d;
           skern_set_[slot] = 1;
           bt.gpu = true;
         }
@@ -1403,29 +1288,13 @@ struct DeviceXetPull::Impl {
     out.results.resize(it.segs.size());
     if (it.failed) {
       out.err = it.err.empty() ? "fetch failed" : it.err;
-      for (size_t k = 0; k < it.segs.size(); ++k)
-        for (size_t t = 0; t < it.at.sources[k].size(); ++t) {
-          const TermSource& ts = it.at.sources[k][t];
-          if (!it.at.planned_ok[k])
-            sh_->bridge->settle(it.segs[k].rec->terms[it.segs[k].t0 + t].hash_hex, ts.src, ts.run_offset, ts.pending,
-                                false);
-          else if (ts.src == Source::Peer && !ts.pending.empty())
-            sh_->bridge->settle(std::string(), ts.src, ts.run_offset, ts.pending, false);
-        }
+      for (size_t k = 0; k < it.segs.size(); ++k) {
+        if (!it.at.planned_ok[k]) drop_runs(it.segs[k], it.at.sources[k]);
+        else drop_quarantined(it.at.sources[k]);
+      }
       return out;
     }
-    for (size_t k = 0; k < it.segs.size(); ++k) {
-      TermJobResult& r = out.results[k];
-      r.chunk_lens = std::move(it.at.chunk_lens[k]);
-      r.fetched = it.at.seg_fetched[k];
-      for (size_t t = 0; t < it.at.sources[k].size(); ++t) {
-        const TermSource& ts = it.at.sources[k][t];
-        const cas::Term& term = it.segs[k].rec->terms[it.segs[k].t0 + t];
-        sh_->book.add(it.jobs[k].xet_hash, term.hash_hex, ts.src, ts.run_offset, ts.pending);
-        (ts.src == Source::Peer ? r.from_peer : ts.src == Source::Cache ? r.from_cache : r.from_cdn) +=
-            term.unpacked_length;
-      }
-    }
+    for (size_t k = 0; k < it.segs.size(); ++k) out.results[k] = book_seg(it.jobs[k].xet_hash, it.segs[k], it.at, k);
     return out;
   }
 
@@ -1508,12 +1377,6 @@ struct DeviceXetPull::Impl {
   uint64_t first_batch_cap() const {
     static const uint64_t mb = env_size("ZEST_FIRST_BATCH_MB", 128);
     return mb ? std::min<uint64_t>(cap_, mb << 20) : cap_;
-  }
-
-  // Upper bound of a term's fetched bytes: Xet stores a chunk uncompressed when compression does
-  // not help, so the payload is <= its unpacked size plus LZ4 frame overhead; + 8-byte headers.
-  static uint64_t term_bound(uint64_t unpacked, uint64_t nchunks) {
-    return unpacked + unpacked / 128 + 80 * nchunks + 4096;
   }
 
   void grow_staging(uint64_t bytes) {

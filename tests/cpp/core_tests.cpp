@@ -516,6 +516,98 @@ TEST(copy_ranges_skip_holes) {
   CHECK(zest::copy_ranges({}, {}, 1).empty());
 }
 
+TEST(plan_pass_layout) {
+  const PassPlan none = plan_pass({});
+  CHECK(none.terms.empty() && none.seg_dst0.empty() && none.seg_chunk0 == std::vector<uint64_t>{0});
+  CHECK(none.base == 0 && none.span == 0 && none.n_chunks == 0);
+  CHECK(plan_batches(none.terms, none.n_chunks, 100, 100).empty());
+  // a segment with no terms lays out nothing of its own
+  const PassPlan bare = plan_pass({{4096, 9, 2, {}}});
+  CHECK(bare.terms.empty() && bare.base == 4096 && bare.span == 0 && bare.n_chunks == 0);
+  CHECK((bare.seg_chunk0 == std::vector<uint64_t>{0, 0}));
+  // two segments, the second below the first in memory and starting at term 3 of its file
+  const PassPlan p = plan_pass({{5000, 7, 0, {{100, 2}, {50, 1}}}, {1000, 10, 3, {{300, 4}}}});
+  CHECK(p.base == 1000 && p.span == 4150 && p.n_chunks == 7);
+  CHECK((p.seg_dst0 == std::vector<uint64_t>{4000, 0}));
+  CHECK((p.seg_chunk0 == std::vector<uint64_t>{0, 3, 7}));
+  CHECK(p.terms.size() == 3);
+  auto same = [](const PassTerm& a, const PassTerm& b) {
+    return a.seg == b.seg && a.term == b.term && a.dst == b.dst && a.chunk == b.chunk && a.nchunks == b.nchunks &&
+           a.ulen == b.ulen;
+  };
+  CHECK(same(p.terms[0], {0, 0, 4000, 0, 2, 100}));
+  CHECK(same(p.terms[1], {0, 1, 4100, 2, 1, 50}));
+  CHECK(same(p.terms[2], {1, 3, 0, 3, 4, 300}));
+  // the second segment's chunk0 must be 7 + 3
+  CHECK_THROWS(plan_pass({{5000, 7, 0, {{100, 2}, {50, 1}}}, {1000, 11, 3, {{300, 4}}}}), "InvalidArgument");
+  CHECK_THROWS(plan_pass({{5000, 7, 0, {{100, 2}, {50, 1}}}, {1000, 9, 3, {{300, 4}}}}), "InvalidArgument");
+}
+
+TEST(plan_batches_rules) {
+  CHECK(term_bound(1000, 1) == 1000 + 7 + 80 + 4096);
+  CHECK(term_bound(0, 0) == 4096);
+  const uint64_t b = term_bound(1000, 1);
+  auto terms_of = [](const std::vector<TermShape>& shapes) { return plan_pass({{0, 0, 0, shapes}}); };
+  // which terms share a batch, as "{0,1}{2}"
+  auto groups = [](const std::vector<PlannedBatch>& bs) {
+    std::string s;
+    for (const auto& x : bs) {
+      s += "{";
+      for (size_t i = x.begin; i < x.end; ++i) s += (i > x.begin ? "," : "") + std::to_string(i);
+      s += "}";
+    }
+    return s;
+  };
+  // the invariants of every plan: batches tile the terms and the chunks, regions are the running
+  // sum of the bounds from 0, the sums and the largest bound are those of the batch's terms
+  auto sound = [](const PassPlan& p, const std::vector<PlannedBatch>& bs) {
+    size_t next = 0;
+    uint64_t chunk = 0;
+    for (const auto& x : bs) {
+      if (x.begin != next || x.end <= x.begin || x.c_lo != chunk || x.off.size() != x.end - x.begin) return false;
+      uint64_t pos = 0, ub = 0, mb = 0;
+      for (size_t i = x.begin; i < x.end; ++i) {
+        if (x.off[i - x.begin] != pos) return false;
+        const uint64_t bound = term_bound(p.terms[i].ulen, p.terms[i].nchunks);
+        pos += bound;
+        ub += p.terms[i].ulen;
+        mb = std::max(mb, bound);
+        chunk += p.terms[i].nchunks;
+      }
+      if (x.ubytes != ub || x.max_bound != mb || x.c_hi != chunk) return false;
+      next = x.end;
+    }
+    return next == p.terms.size() && chunk == p.n_chunks;
+  };
+  // an exact fit stays in its batch; one byte less and it does not
+  const PassPlan three = terms_of({{1000, 1}, {1000, 1}, {1000, 1}});
+  auto fit = plan_batches(three.terms, three.n_chunks, 2 * b, 2 * b);
+  CHECK(groups(fit) == "{0,1}{2}" && sound(three, fit));
+  CHECK((fit[0].off == std::vector<uint64_t>{0, b}) && (fit[1].off == std::vector<uint64_t>{0}));
+  CHECK(fit[0].c_lo == 0 && fit[0].c_hi == 2 && fit[1].c_lo == 2 && fit[1].c_hi == 3);
+  CHECK(fit[0].ubytes == 2000 && fit[1].ubytes == 1000 && fit[0].max_bound == b);
+  auto tight = plan_batches(three.terms, three.n_chunks, 2 * b - 1, 2 * b - 1);
+  CHECK(groups(tight) == "{0}{1}{2}" && sound(three, tight));
+  // the first cap holds for batch 0 only
+  const PassPlan four = terms_of({{1000, 1}, {1000, 1}, {1000, 1}, {1000, 1}});
+  auto first = plan_batches(four.terms, four.n_chunks, b, 3 * b);
+  CHECK(groups(first) == "{0}{1,2,3}" && sound(four, first));
+  CHECK((first[1].off == std::vector<uint64_t>{0, b, 2 * b}));
+  // a term over the cap is a batch of one, between its neighbours' batches, and reports its bound
+  const PassPlan big = terms_of({{1000, 1}, {200000, 3}, {1000, 1}, {500, 2}});
+  auto over = plan_batches(big.terms, big.n_chunks, 2 * b, 2 * b);
+  CHECK(groups(over) == "{0}{1}{2,3}" && sound(big, over));
+  CHECK(over[1].max_bound == term_bound(200000, 3) && over[1].max_bound > 2 * b);
+  CHECK(over[1].c_lo == 1 && over[1].c_hi == 4 && over[2].c_hi == 7 && big.n_chunks == 7);
+  // ... also as the pass's first term under a first cap
+  auto over0 = plan_batches(big.terms, big.n_chunks, 1, 1);
+  CHECK(groups(over0) == "{0}{1}{2}{3}" && sound(big, over0));
+  // terms without chunks (empty ranges) keep the chunk ranges tiling
+  const PassPlan holes = terms_of({{0, 0}, {1000, 2}, {0, 0}});
+  auto hb = plan_batches(holes.terms, holes.n_chunks, b, b);
+  CHECK(sound(holes, hb) && hb.back().c_hi == 2);
+}
+
 TEST(peer_pool_leases) {
   // Lease accounting of the connection pool against a loopback seeding server: a lease raises its
   // session's user count by exactly one for its lifetime, busy sessions make the pool open more

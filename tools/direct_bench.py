@@ -102,6 +102,11 @@ def main() -> int:
     hub = FakeHub()
     hub.start()
     commit = hub.add_world(world, exact=True, payload=False)
+    # Runs that the write-behind cache queue drops (a 16 GB pull outruns the disk) are refetched from
+    # the CDN when the pipeline goes.  This hub has no xorb payload to serve, and it is served by this
+    # process: the pipeline is destroyed with the GIL held, so each such request would wait out its
+    # 120 s HTTP timeout before the hub thread could answer 404.
+    os.environ["ZEST_CACHE_REFILL"] = "0"
     total = world.model_bytes
     print(f"[setup] {spec.repo_id}: {total / 1e9:.2f} GB, {world.n_chunks} chunks, {world.n_xorbs} xorbs in HBM "
           f"({time.time() - t0:.1f}s)", flush=True)
