@@ -290,4 +290,25 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("src"), py::arg("table"), py::arg("n"), py::arg("dst_total"), py::arg("dst"), py::arg("stream"),
      "K10: table is a device block of SLICE_ROWS rows of n uint64 (src_off, run_bytes, src_stride, n_runs, "
      "dst_off, dst_end), pre-validated by the caller (zest_amd.ops.slice_gather)");
+  m.attr("SLICE_PEER_ROWS") = int(ZG_SLICE_PEER_ROWS);
+  m.attr("MAX_SLICE_SRCS") = int(kZgMaxPeerSegs);
+  m.def("slice_gather_peers", [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& lo,
+                                 const std::vector<uint64_t>& hi, uintptr_t table, uint32_t n, uint64_t dst_total,
+                                 uintptr_t dst, uint32_t max_blocks, uintptr_t st) {
+    if (src.size() != lo.size() || src.size() != hi.size() || src.size() > size_t(kZgMaxPeerSegs))
+      throw std::invalid_argument("slice_gather_peers: need equal-length src/lo/hi lists of at most 16 sources");
+    ZgSliceSrcs s{};
+    s.nseg = int(src.size());
+    for (size_t i = 0; i < src.size(); ++i) {
+      if (hi[i] < lo[i] || hi[i] > dst_total) throw std::invalid_argument("slice_gather_peers: bad arena range");
+      s.src[i] = src[i];
+      s.lo[i] = lo[i];
+      s.hi[i] = hi[i];
+    }
+    check(zg_slice_gather_peers(&s, P<const uint64_t>(table), n, dst_total, P<uint8_t>(dst), max_blocks, S(st)),
+          "zg_slice_gather_peers");
+  }, py::arg("src"), py::arg("lo"), py::arg("hi"), py::arg("table"), py::arg("n"), py::arg("dst_total"),
+     py::arg("dst"), py::arg("max_blocks"), py::arg("stream"),
+     "K11: K10 over several sources; table has SLICE_PEER_ROWS rows (K10's plus each entry's source index), "
+     "[lo[s], hi[s]) is source s's arena range; pre-validated by the caller (zest_amd.ops.slice_gather_peers)");
 }

@@ -208,6 +208,23 @@ typedef struct ZgPeerSegs {
 } ZgPeerSegs;
 hipError_t zg_peer_gather(const ZgPeerSegs* segs, hipStream_t stream);
 
+// K11 (shard_peers.hip): K10 over up to kZgMaxPeerSegs source buffers in one launch.  table: K10's
+// rows plus row ZG_SLICE_SRC, the source index of each entry (ZG_SLICE_PEER_ROWS rows of n uint64);
+// src_off is relative to src[that index].  Beyond K10's preconditions the entries of one source are
+// contiguous in the table; [lo[s], hi[s]) is the arena range from the first dst_off to the last
+// dst_end of source s's entries with output (lo == hi: none).  Neighbouring blocks serve
+// different sources and a block loops over its source's tiles; max_blocks caps the grid (0: 512, as K8; at least one block per
+// source).  Nothing is checked on the device beyond hi <= dst_total.
+enum { ZG_SLICE_SRC = 6, ZG_SLICE_PEER_ROWS = 7 };
+typedef struct ZgSliceSrcs {
+  uint64_t src[kZgMaxPeerSegs];
+  uint64_t lo[kZgMaxPeerSegs];
+  uint64_t hi[kZgMaxPeerSegs];
+  int nseg;
+} ZgSliceSrcs;
+hipError_t zg_slice_gather_peers(const ZgSliceSrcs* srcs, const uint64_t* table, uint32_t n, uint64_t dst_total,
+                                 uint8_t* dst, uint32_t max_blocks, hipStream_t stream);
+
 int zg_device_count(void);
 // K6: out[i] (20 B) = SHA1("zest-xet-v1:" || hashes[i] (32 B)); out must be 4-byte aligned.
 hipError_t zg_sha1_info_hash(const uint8_t* hashes, int n, uint8_t* out, hipStream_t stream);

@@ -392,7 +392,7 @@ def main():
             H.host_free(host)
         del d_out
 
-    if want("slice_gather"):
+    if want("slice_gather") or want("slice_gather_peers"):
         # K10 slice_gather: one Llama-3.1-70B safetensors shard, rank 0 of 8 under the "llama-tp" plan,
         # next to its roof (a device-to-device copy of the kept bytes: read N + write N) and to what it
         # replaces (narrow(...).contiguous() per kept tensor); alternated, three rounds
@@ -425,11 +425,39 @@ def main():
         # contiguous() copies only the dim-1 slices: a dim-0 slice is contiguous already and stays a view
         # into the file buffer, which then cannot be freed.  The clone loop gives every kept tensor its
         # own memory, as the kernel does: that is the like-for-like row.
+        k10 = ("slice_gather[kernel]", lambda: H.slice_gather(fbuf.data_ptr(), tab_d.data_ptr(), tab.shape[1],
+                                                              int(tab[5, -1]), out.data_ptr(), st))
         rows = (("torch_narrow_clone_loop", lambda: torch_loop(lambda t: t.clone(memory_format=torch.contiguous_format))),("slice_gather[ops]", lambda: ops.slice_gather(fbuf, plan.table, out)),
-                ("slice_gather[kernel]", lambda: H.slice_gather(fbuf.data_ptr(), tab_d.data_ptr(), tab.shape[1],
-                                                                int(tab[5, -1]), out.data_ptr(), st)),
+                k10,
                 ("d2d_copy_of_kept_bytes", lambda: flat.copy_(fbuf[:kept])),
-                ("torch_narrow_contiguous_loop", torch_loop))
+                ("torch_narrow_contiguous_loop", torch_loop)) if want("slice_gather") else (k10,)
+        if want("slice_gather_peers"):
+            # K11 slice_gather_peers on the same table, in the same process as K10: one source, and the
+            # file cut into 8 equal source buffers on this one GPU (entry i reads from the eighth that
+            # holds its first byte); under the default grid cap (512 blocks) and with the cap lifted
+            out11 = torch.zeros_like(out)
+            live = np.flatnonzero(tab[1] * tab[3])
+            span = (int(tab[4, live[0]]), int(tab[5, live[-1]]))
+
+            def peers_row(nsrc, max_blocks):
+                cut = -(-sf.size // nsrc)
+                t = np.empty((H.SLICE_PEER_ROWS, tab.shape[1]), dtype=np.uint64)
+                t[:6] = tab
+                t[6] = tab[0] // cut
+                t[0] = tab[0] - t[6] * cut
+                assert (np.diff(t[6].astype(np.int64)) >= 0).all()  # each source's entries are contiguous
+                lo, hi = [0] * nsrc, [0] * nsrc
+                for s_ in range(nsrc):
+                    mine = [i for i in live if t[6, i] == s_]
+                    if mine:
+                        lo[s_], hi[s_] = int(t[4, mine[0]]), int(t[5, mine[-1]])
+                t_d = torch.from_numpy(t.view(np.int64)).to(dev)
+                bases = [fbuf.data_ptr() + s_ * cut for s_ in range(nsrc)]
+                return lambda: H.slice_gather_peers(bases, lo, hi, t_d.data_ptr(), t.shape[1], span[1],
+                                                    out11.data_ptr(), max_blocks, st)
+
+            rows += tuple((f"slice_gather_peers[{ns}src,{'cap512' if mb == 0 else 'lifted'}]", peers_row(ns, mb))
+                          for ns in (1, 8) for mb in (0, 1 << 20))
         for rnd in range(3):
             for name, fn in rows:
                 ms = timed(fn, a.iters)
@@ -438,6 +466,13 @@ def main():
         got = plan.views(out)
         for nm, t in zip(acts, torch_loop()):
             assert torch.equal(got[nm].view(torch.uint8), t.reshape(got[nm].shape).view(torch.uint8)), nm
+        if want("slice_gather_peers"):
+            for _, fn in rows[-4:]:  # every variant rewrites the whole arena
+                out11.zero_()
+                fn()
+                got11 = plan.views(out11)
+                assert all(torch.equal(got[nm].view(torch.uint8), got11[nm].view(torch.uint8)) for nm in acts)
+            del out11, got11
         del out, flat, tab_d, views, got
 
     if want("h2d"):

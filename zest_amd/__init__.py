@@ -84,7 +84,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       are seeded to BEP XET peers straight from the HBM the returned tensors occupy -- no serialized
       copy, no disk (zest_amd.seed.ResidentSeedServer; `zest_amd.seed.active()` lists the servers,
       `zest_amd.seed.stop_all()` / `zest_amd.stop()` stop them).  Keep the tensors read-only meanwhile.
-    * shard=Shard(rank, world, plan) or (rank, world), device="cuda:N" / "cpu" direct pulls only: the
+    * shard=Shard(rank, world, plan) or (rank, world), device="cuda:N" / "cpu" direct pulls: the
       returned tensors are this rank's slices (tensor-parallel parts, a pipeline stage, its experts:
       zest_amd.shard) and only they stay in device memory.  Every file is still pulled and verified
       whole, through a reused scratch of `scratch_bytes` (default: the larger of the largest file and
@@ -92,14 +92,35 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       bounds device memory, not network bytes.  Files in which the rank keeps nothing (per
       model.safetensors.index.json) are not fetched.  `stats["shard"]` receives file_bytes, kept_bytes,
       skipped_files, groups, scratch_bytes and gather_s.
+    * shard= with device="all": the collective sharded pull over `group` (default WORLD; start one
+      process per GPU and call zest_amd.parallel.init_from_env() first).  The shard's rank and world
+      must be the group's.  Each file is fetched and verified whole by one owner rank and every rank
+      takes only its own slices out of the owner's memory, so each file crosses the network once per
+      group and only kept slices cross xGMI (zest_amd.parallel.shard_pull).  `exchange`: "auto",
+      "mapped" (GPUs: one gather launch over the peer-mapped scratches) or "send" (gather on the
+      owner, then all-to-all; any backend, CPU groups).  ZEST_SHARD_CROSSCHECK=1 runs both and compares
+      every kept byte.  `stats["shard"]` also receives exchange, rounds, owned_files, fetched_bytes,
+      received_bytes and p2p_ratio.  seed=, save_snapshot=True and direct=False stay refused.
     """
     if shard is not None:
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu'); a snapshot pull has no tensors "
                              "to slice")
         if device == "all":
-            raise ValueError("shard= is not supported with device='all': run one process per GPU with "
-                             "device='cuda:N' (a collective sharded pull does not exist yet)")
+            import torch.distributed as dist
+
+            if group is None and not (dist.is_available() and dist.is_initialized()):
+                raise ValueError("shard= with device='all' is a collective: start one process per GPU (torchrun), "
+                                 "call zest_amd.parallel.init_from_env() in each, then pull(device='all', "
+                                 "shard=(rank, world)); without a process group use device='cuda:N'")
+            if seed is not False and seed is not None:
+                raise ValueError("shard= is not supported with seed=: the file bytes do not stay resident; seed "
+                                 "from an unsharded pull")
+            if save_snapshot:
+                raise ValueError("shard= is not supported with save_snapshot=True: whole files never stay in "
+                                 "memory; write the snapshot with a plain pull(repo)")
+            if exchange not in ("auto", "mapped", "send"):
+                raise ValueError(f"exchange={exchange!r}: a collective sharded pull takes auto, mapped or send")
         if direct is False:
             raise ValueError("shard= is not supported with direct=False (the snapshot path): use the default "
                              "device-direct pull")
@@ -117,6 +138,13 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
               verify=verify, repo_type=repo_type, verbose=verbose)
     if device is None and not as_tensors:
         return _client.pull(repo, revision, **kw)
+    if device == "all" and shard is not None:
+        from .parallel import swarm_pull_sharded
+
+        return swarm_pull_sharded(repo, revision, group=group, shard=shard, scratch_bytes=scratch_bytes,
+                                  exchange=exchange, stats=stats, p2p=p2p, peers=peers, tracker=tracker, dht=dht,
+                                  dht_bootstrap=dht_bootstrap, repo_type=repo_type, staging_bytes=staging_bytes,
+                                  threads=threads, include=include)
     if device == "all":
         from .parallel import swarm_pull
 

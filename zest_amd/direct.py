@@ -25,8 +25,9 @@ rank's tensor slices stay in device memory.  Files are still pulled and verified
 hash covers every chunk of the file) through one reused scratch of `scratch_bytes`, then
 `ops.slice_gather` copies the kept slices into a compact arena per file; files in which the rank
 keeps nothing (per `model.safetensors.index.json`) are not fetched.  It bounds device memory, not
-network bytes.  `stats["shard"]` receives file_bytes, kept_bytes, skipped_files, groups,
-scratch_bytes and gather_s.
+network bytes (the collective `pull(device="all", shard=...)`, zest_amd.parallel.shard_pull,
+does).  `stats["shard"]` receives file_bytes, kept_bytes, skipped_files, groups, scratch_bytes and
+gather_s.
 """
 from __future__ import annotations
 
@@ -48,8 +49,9 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu')")
         if device == "all":
-            raise ValueError("shard= is not supported with device='all': run one process per GPU with "
-                             "device='cuda:N' (a collective sharded pull does not exist yet)")
+            raise ValueError("pull_to_device is the single-process pull: with shard= run one process per GPU with "
+                             "device='cuda:N', or the collective zest_amd.pull(device='all', shard=...) "
+                             "(zest_amd.parallel.swarm_pull_sharded)")
         if seed is not False and seed is not None:
             raise ValueError("shard= is not supported with seed=: the file bytes do not stay resident; seed from "
                              "an unsharded pull")
@@ -167,20 +169,6 @@ def _pull_sharded(repo, revision, dev, sh, scratch_bytes, stats, *, p2p, peers, 
             "gather_s": 0.0}
     timed = []  # cuda: (start, end) events around each group's gathers, read once at the end
 
-    def gather(buf: torch.Tensor, path: str) -> None:
-        """Plan one verified file in `buf`, gather the kept slices into a new arena, add the views."""
-        (hlen,) = struct.unpack("<Q", buf[:8].cpu().numpy().tobytes())
-        start, meta = zdev.parse_safetensors_header(buf[:8 + hlen].cpu().numpy().tobytes())
-        plan = zshard.plan_file(start, meta, sh, buf.numel())
-        arena = ops.padded_empty(plan.arena_bytes, dev) if cuda else torch.empty(plan.arena_bytes, dtype=torch.uint8)
-        ops.slice_gather(buf, plan.table, arena)
-        for k, v in plan.views(arena).items():
-            if k in out:
-                raise ValueError(f"duplicate tensor {k} in {path}")
-            out[k] = v
-        info["file_bytes"] += buf.numel()
-        info["kept_bytes"] += sum(t.nbytes for t in plan.tensors)
-
     if xet:
         biggest = max(_slot(f["size"]) for f in xet)
         want = max(max(f["size"] for f in xet), DEFAULT_SCRATCH) if scratch_bytes is None else int(scratch_bytes)
@@ -199,7 +187,7 @@ def _pull_sharded(repo, revision, dev, sh, scratch_bytes, stats, *, p2p, peers, 
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record()
                     for f, o in g:
-                        gather(scratch[o:o + f["size"]], f["path"])
+                        _gather_file(scratch[o:o + f["size"]], f["path"], sh, dev, out, info)
                     ev1.record()
                     timed.append((ev0, ev1))
                     # The next group overwrites the scratch these gathers read.  Only the pipeline's
@@ -214,27 +202,52 @@ def _pull_sharded(repo, revision, dev, sh, scratch_bytes, stats, *, p2p, peers, 
                 hf.fetch_files([(f["xet_hash"], scratch.data_ptr() + o, f["size"]) for f, o in g])
                 t0 = time.perf_counter()
                 for f, o in g:
-                    gather(scratch[o:o + f["size"]], f["path"])
+                    _gather_file(scratch[o:o + f["size"]], f["path"], sh, dev, out, info)
                 info["gather_s"] += time.perf_counter() - t0
-    if plain:  # non-Xet safetensors: the host route, then the same plan and gather
-        r = _core.pull(repo, revision, *net, [f["path"] for f in plain], True, 0, repo_type)
-        for f in plain:
-            buf = zdev.load_file(os.path.join(r["snapshot_dir"], f["path"]), dev)
-            t0 = time.perf_counter()
-            if cuda:
-                with torch.cuda.device(dev):
-                    gather(buf, f["path"])
-                    torch.cuda.current_stream(dev).synchronize()  # buf is freed before the next file loads
-            else:
-                gather(buf, f["path"])
-            info["gather_s"] += time.perf_counter() - t0
-            del buf
+    if plain:
+        _pull_plain_sharded(repo, revision, net, repo_type, plain, dev, sh, out, info)
     if timed:
         torch.cuda.synchronize(dev)
         info["gather_s"] += sum(a.elapsed_time(b) for a, b in timed) / 1e3
     if stats is not None:
         stats["shard"] = info
     return out
+
+
+def _gather_file(buf: torch.Tensor, path: str, sh, dev, out: dict, info: dict) -> None:
+    """Plan one verified file in `buf` for `sh`, gather the kept slices into a new arena and add the
+    views to `out`; counts file_bytes and kept_bytes in `info`."""
+    (hlen,) = struct.unpack("<Q", buf[:8].cpu().numpy().tobytes())
+    start, meta = zdev.parse_safetensors_header(buf[:8 + hlen].cpu().numpy().tobytes())
+    plan = zshard.plan_file(start, meta, sh, buf.numel())
+    arena = ops.padded_empty(plan.arena_bytes, dev) if dev.type == "cuda" else \
+        torch.empty(plan.arena_bytes, dtype=torch.uint8)
+    ops.slice_gather(buf, plan.table, arena)
+    for k, v in plan.views(arena).items():
+        if k in out:
+            raise ValueError(f"duplicate tensor {k} in {path}")
+        out[k] = v
+    info["file_bytes"] += buf.numel()
+    info["kept_bytes"] += sum(t.nbytes for t in plan.tensors)
+
+
+def _pull_plain_sharded(repo, revision, net, repo_type, plain, dev, sh, out: dict, info: dict) -> None:
+    """Non-Xet safetensors of a sharded pull (single-process and collective alike): the host route,
+    then the same plan and gather, file by file.  Adds the gather time to info["gather_s"]."""
+    import time
+
+    r = _core.pull(repo, revision, *net, [f["path"] for f in plain], True, 0, repo_type)
+    for f in plain:
+        buf = zdev.load_file(os.path.join(r["snapshot_dir"], f["path"]), dev)
+        t0 = time.perf_counter()
+        if dev.type == "cuda":
+            with torch.cuda.device(dev):
+                _gather_file(buf, f["path"], sh, dev, out, info)
+                torch.cuda.current_stream(dev).synchronize()  # buf is freed before the next file loads
+        else:
+            _gather_file(buf, f["path"], sh, dev, out, info)
+        info["gather_s"] += time.perf_counter() - t0
+        del buf
 
 
 def _add_views(out: dict, buf: torch.Tensor, path: str) -> None:

@@ -6,7 +6,7 @@ bad descriptor can never become an out-of-bounds GPU access.  GPU tensors always
 CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/CPU tests use.
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
-K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather.
+K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers.
 """
 from __future__ import annotations
 
@@ -626,26 +626,27 @@ SLICE_DTYPE = np.dtype([("src_off", "<u8"), ("run_bytes", "<u8"), ("src_stride",
 SLICE_ALIGN = 16  # what the kernel relies on for dst and every dst_off (zest_amd.shard hands out 256)
 
 
-def _check_slice_table(table, src_n: int, dst_n: int) -> tuple[np.ndarray, np.ndarray]:
-    """Validate a slice table against its buffers; returns (table, output bytes per entry)."""
+def _check_slice_table(table, src_n: int, dst_n: int, what: str = "slice_gather: ",
+                       end: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """Validate a slice table against its buffers; returns (table, output bytes per entry).  `what`
+    opens every message; `end` is where the outputs before this table end (slice_gather_peers)."""
     table = np.ascontiguousarray(table, dtype=SLICE_DTYPE).reshape(-1)
     big = lambda f: [int(x) for x in table[f]]  # Python ints: no uint64 wrap-around in the checks
     so, rb, st, nr, do = (big(f) for f in SLICE_DTYPE.names)
     size = []
-    end = 0  # end of the outputs so far
     for i in range(len(table)):
         n = rb[i] * nr[i]
         size.append(n)
         if n and st[i] < rb[i]:
-            raise ValueError(f"slice_gather: entry {i}: src_stride {st[i]} < run_bytes {rb[i]}")
+            raise ValueError(f"{what}entry {i}: src_stride {st[i]} < run_bytes {rb[i]}")
         if n and so[i] + (nr[i] - 1) * st[i] + rb[i] > src_n:
-            raise ValueError(f"slice_gather: entry {i}: runs reach past the source ({src_n} bytes)")
+            raise ValueError(f"{what}entry {i}: runs reach past the source ({src_n} bytes)")
         if do[i] % SLICE_ALIGN:
-            raise ValueError(f"slice_gather: entry {i}: dst_off {do[i]} is not {SLICE_ALIGN}-byte aligned")
+            raise ValueError(f"{what}entry {i}: dst_off {do[i]} is not {SLICE_ALIGN}-byte aligned")
         if do[i] + n > dst_n:
-            raise ValueError(f"slice_gather: entry {i}: output reaches past the arena ({dst_n} bytes)")
+            raise ValueError(f"{what}entry {i}: output reaches past the arena ({dst_n} bytes)")
         if do[i] < end:
-            raise ValueError(f"slice_gather: entry {i}: dst_off {do[i]} overlaps or precedes the entry before it")
+            raise ValueError(f"{what}entry {i}: dst_off {do[i]} overlaps or precedes the entry before it")
         end = do[i] + n
     return table, np.asarray(size, dtype=np.uint64)
 
@@ -685,6 +686,76 @@ def slice_gather(src: torch.Tensor, table, dst: torch.Tensor, stream=None) -> No
         with torch.cuda.stream(stream):  # the table's upload and its free are ordered on the launch's stream
             tab = _dev_array(soa, src.device)
     H.slice_gather(src.data_ptr(), tab.data_ptr(), n, int(soa[5, -1]), dst.data_ptr(), st)
+
+
+MAX_SLICE_SRCS = 16  # kZgMaxPeerSegs: source bases travel by value in the kernel's arguments
+
+
+def slice_gather_peers(srcs, tables, dst: torch.Tensor, stream=None, max_blocks: int = 0) -> None:
+    """:func:`slice_gather` out of several source buffers in one launch: K11, csrc/gpu/shard_peers.hip
+    (a round of the collective sharded pull reads the owners' scratches, its own and its peers').
+
+    srcs: up to 16 contiguous uint8 tensors on dst's device.  tables: one SLICE_DTYPE table per
+    source; src_off is relative to that source, dst_off is absolute in `dst` and ascends across the
+    concatenation of the tables, so each source owns one range of the arena.  A table may be empty.
+    Validation is slice_gather's, per source against that source's length and globally for order,
+    disjointness and alignment: a ValueError names the source and the entry before anything is
+    launched.  Only the outputs are written.  GPU: one asynchronous launch on `stream` whose blocks
+    interleave the sources; `max_blocks` caps the grid (0: the kernel's default of 512, which leaves
+    room for the kernels of the next round's pull).  CPU tensors: the NumPy path, source by source."""
+    srcs, tables = list(srcs), list(tables)
+    if len(srcs) != len(tables):
+        raise ValueError(f"slice_gather_peers: {len(srcs)} sources but {len(tables)} tables")
+    if len(srcs) > MAX_SLICE_SRCS:
+        raise ValueError(f"slice_gather_peers: {len(srcs)} sources, at most {MAX_SLICE_SRCS}")
+    if dst.dtype != torch.uint8 or not dst.is_contiguous():
+        raise ValueError("slice_gather_peers: dst must be a contiguous uint8 tensor")
+    for s, src in enumerate(srcs):
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError(f"slice_gather_peers: source {s} must be a contiguous uint8 tensor")
+        if src.device != dst.device:
+            raise ValueError(f"slice_gather_peers: source {s} is on {src.device}, dst on {dst.device}")
+    if int(max_blocks) < 0:
+        raise ValueError("slice_gather_peers: max_blocks must be >= 0")
+    checked, end = [], 0
+    for s, (src, table) in enumerate(zip(srcs, tables)):
+        table, size = _check_slice_table(table, src.numel(), dst.numel(), f"slice_gather_peers: source {s} ", end)
+        if len(table):
+            end = int(table["dst_off"][-1]) + int(size[-1])
+        checked.append((table, size))
+    if not any(size.any() for _, size in checked):
+        return
+    if dst.device.type != "cuda":
+        d = dst.reshape(-1).numpy()
+        for src, (table, _) in zip(srcs, checked):
+            _slice_gather_cpu(src.reshape(-1).numpy(), table, d)
+        return
+    if dst.data_ptr() % SLICE_ALIGN:
+        raise ValueError(f"slice_gather_peers: dst must be {SLICE_ALIGN}-byte aligned")
+    H = hip()
+    n = sum(len(t) for t, _ in checked)
+    soa = np.empty((H.SLICE_PEER_ROWS, n), dtype=np.uint64)
+    lo, hi, pos = [], [], 0
+    for s, (table, size) in enumerate(checked):
+        k = len(table)
+        for r, f in enumerate(SLICE_DTYPE.names):
+            soa[r, pos:pos + k] = table[f]
+        ends = table["dst_off"] + size
+        soa[5, pos:pos + k] = ends
+        soa[6, pos:pos + k] = s
+        live = np.flatnonzero(size)  # the source's arena range: its entries with output
+        lo.append(int(table["dst_off"][live[0]]) if live.size else 0)
+        hi.append(int(ends[live[-1]]) if live.size else 0)
+        pos += k
+    if stream is None:
+        st = _stream(dst.device)
+        tab = _dev_array(soa, dst.device)
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the table's upload and its free are ordered on the launch's stream
+            tab = _dev_array(soa, dst.device)
+    H.slice_gather_peers([src.data_ptr() for src in srcs], lo, hi, tab.data_ptr(), n, int(soa[5, -1]),
+                         dst.data_ptr(), int(max_blocks), st)
 
 
 def _slice_gather_cpu(src: np.ndarray, table: np.ndarray, dst: np.ndarray) -> None:

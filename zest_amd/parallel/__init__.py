@@ -8,6 +8,9 @@
 * `swarm_pull`: the same machinery fed by the network (public `pull(device="all")`): byte-balanced
   term shares fetched device-direct, rounds exchanged over xGMI, every chunk re-hashed on every GPU,
   Merkle-checked per file; survives a lost rank.
+* `swarm_pull_sharded`: the collective sharded pull (public `pull(device="all", shard=...)`): each
+  file fetched and verified by one owner rank, every rank gathers only its own slices out of the
+  owners' scratches (K11 over peer-mapped arenas, or K10 + all-to-all).
 * `swarm_load`: replicate a pulled snapshot into every GPU's HBM, each file read by one owner rank.
 * `init_from_env`: torchrun-style rendezvous (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*).
 * `bind_local_numa`: pin a rank to the CPUs of its GPU's NUMA node, so its pinned host staging and
@@ -21,6 +24,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from .shard_pull import ShardPullError, swarm_pull_sharded
 from .swarm_load import assign_owners, swarm_load
 from .swarm_pull import SwarmPullError, swarm_pull
 
@@ -107,4 +111,4 @@ def __getattr__(name):
 
 
 __all__ = ["DevicePuller", "assign_owners", "bind_local_numa", "gpu_local_cpus", "init_from_env", "nccl_options",
-           "parse_cpulist", "swarm_load", "swarm_pull", "SwarmPullError"]
+           "parse_cpulist", "swarm_load", "swarm_pull", "swarm_pull_sharded", "ShardPullError", "SwarmPullError"]
