@@ -180,8 +180,9 @@ class HostXetFetcher {
     return zest::cached_terms(*cache_, hexes, starts, ends, threads_);
   }
   void reset_reconstructions() { recs_->clear(); }
-  std::vector<TermJobResult> fetch_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, bool repair) {
-    return fetch_terms_host(*bridge_, *recs_, book_, jobs, hashes, threads_, repair);
+  std::vector<TermJobResult> fetch_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, bool repair,
+                                         bool share_runs = false) {
+    return fetch_terms_host(*bridge_, *recs_, book_, jobs, hashes, threads_, repair, share_runs);
   }
   size_t settle(const std::string& hex, bool ok) { return book_.settle(*bridge_, hex, ok); }
   std::vector<FileResult> fetch(const std::vector<std::tuple<std::string, uintptr_t, uint64_t>>& files) {
@@ -710,17 +711,18 @@ void bind_extra(py::module_& m) {
       .def("reset_reconstructions", &HostXetFetcher::reset_reconstructions, "forget cached reconstructions (between pulls)")
       .def("fetch_terms",
            [](HostXetFetcher& self, const std::vector<std::tuple<std::string, uint32_t, uint32_t, uintptr_t, uint64_t>>& v,
-              uintptr_t hashes, bool repair) {
+              uintptr_t hashes, bool repair, bool share_runs) {
              const auto jobs = term_jobs_of(v);
              std::vector<TermJobResult> rs;
              {
                py::gil_scoped_release nogil;
-               rs = self.fetch_terms(jobs, reinterpret_cast<uint8_t*>(hashes), repair);
+               rs = self.fetch_terms(jobs, reinterpret_cast<uint8_t*>(hashes), repair, share_runs);
              }
              return term_results_py(rs);
            },
-           py::arg("jobs"), py::arg("hashes_ptr"), py::arg("repair") = false,
-           "[(xet_hash, t0, t1, dst_ptr, chunk0), ...]: fetch + decode + chunk-hash term ranges into host memory")
+           py::arg("jobs"), py::arg("hashes_ptr"), py::arg("repair") = false, py::arg("share_runs") = false,
+           "[(xet_hash, t0, t1, dst_ptr, chunk0), ...]: fetch + decode + chunk-hash term ranges into host memory; "
+           "share_runs: terms of the call that lie in one CAS fetch entry download it once")
       .def("settle", [](HostXetFetcher& self, const std::string& hex, bool ok) {
              py::gil_scoped_release nogil;
              return self.settle(hex, ok);

@@ -282,6 +282,16 @@ PYBIND11_MODULE(_hip, m) {
           "zg_serve_pack");
   }, py::arg("src_table"), py::arg("ser_end_table"), py::arg("n"), py::arg("lo"), py::arg("hi"), py::arg("out"),
      py::arg("stream"));
+  m.attr("REUSE_BYTES") = sizeof(ZgReuse);
+  m.def("reuse_chunks", [](uintptr_t recs, int n, uintptr_t dst, uintptr_t hashes, uintptr_t sizes, uintptr_t scratch,
+                           size_t scratch_bytes, uintptr_t st) {
+    check(zg_reuse_chunks(P<const ZgReuse>(recs), n, P<uint8_t>(dst), P<uint8_t>(hashes), P<uint64_t>(sizes),
+                          P<uint8_t>(scratch), scratch_bytes, S(st)),
+          "zg_reuse_chunks");
+  }, py::arg("recs"), py::arg("n"), py::arg("dst"), py::arg("hashes"), py::arg("sizes"), py::arg("scratch"),
+     py::arg("scratch_bytes"), py::arg("stream"),
+     "K12: recs is a device array of ZgReuse records (src address, dst offset, len, table row), pre-validated by "
+     "the caller (zest_amd.ops.reuse_chunks)");
   m.attr("SLICE_ROWS") = int(ZG_SLICE_ROWS);
   m.def("slice_gather", [](uintptr_t src, uintptr_t table, uint32_t n, uint64_t dst_total, uintptr_t dst,
                            uintptr_t st) {

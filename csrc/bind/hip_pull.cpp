@@ -116,19 +116,21 @@ void bind_hip_pull(py::module_& m) {
       .def("reset_reconstructions", &DeviceXetPull::reset_reconstructions, "forget cached reconstructions (between pulls)")
       .def("pull_terms",
            [](DeviceXetPull& self, const std::vector<zest::TermJobTuple>& v, uintptr_t hashes, uintptr_t sizes,
-              bool repair) {
+              bool repair, bool share_runs) {
              const auto jobs = zest::term_jobs_of(v);
              std::vector<zest::TermJobResult> rs;
              {
                py::gil_scoped_release nogil;
                rs = self.pull_terms(jobs, reinterpret_cast<uint8_t*>(hashes), reinterpret_cast<uint64_t*>(sizes),
-                                    repair);
+                                    repair, share_runs);
              }
              return zest::term_results_py(rs);
            },
            py::arg("jobs"), py::arg("hashes_ptr"), py::arg("sizes_ptr") = 0, py::arg("repair") = false,
+           py::arg("share_runs") = false,
            "[(xet_hash, t0, t1, dst_ptr, chunk0), ...]: fetch term ranges, GPU decode + chunk-hash them into "
-           "place (hashes/sizes: device tables indexed by chunk); consecutive chunk indices required")
+           "place (hashes/sizes: device tables indexed by chunk); consecutive chunk indices required; share_runs: "
+           "terms of the call that lie in one CAS fetch entry download it once")
       .def("submit_terms",
            [](DeviceXetPull& self, const std::vector<zest::TermJobTuple>& v, uintptr_t hashes, uintptr_t sizes) {
              const auto jobs = zest::term_jobs_of(v);

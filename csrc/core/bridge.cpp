@@ -117,6 +117,52 @@ XorbFetchResult XetBridge::fetch_term(const cas::Term& term, const cas::Reconstr
   }
   // 3. CDN: straight into the sink's memory when it has room (no intermediate buffer)
   if (!cas_) throw Error("NotAuthenticated");
+  // An entry wider than the term serves other terms too: with a memo, one of them downloads it.
+  RunMemo* memo = fi->range.end - fi->range.start > term.range.end - term.range.start ? opt.share.get() : nullptr;
+  // Entries are per file: two files' entries in one xorb may start alike and end apart, so the key
+  // is the whole entry, chunk range and byte range.
+  const RunMemo::Key memo_key(hex, fi->range.start, fi->range.end, fi->url_range.start, fi->url_range.end);
+  bool memo_owner = false;
+  if (memo) {
+    std::unique_lock<std::mutex> g(memo->mu);
+    auto ins = memo->runs.emplace(memo_key, RunMemo::Ent{});
+    memo_owner = ins.second;
+    if (!memo_owner) {
+      memo->cv.wait(g, [&] { return ins.first->second.done; });
+      std::shared_ptr<const Bytes> body = ins.first->second.body;
+      g.unlock();
+      // a body that does not hold the term's chunks is not landed: this fetch downloads its own
+      if (body && covers(body->data(), body->size(), uint32_t(fi->range.start), term.range.start, term.range.end)) {
+        land(out, body->data(), body->size(), nullptr);
+        out.local_start = uint32_t(term.range.start - fi->range.start);
+        out.local_end = uint32_t(term.range.end - fi->range.start);
+        out.source = Source::Cdn;
+        // the term was served from the CDN's bytes: counted like the download it shares
+        stats_.xorbs_from_cdn++;
+        stats_.bytes_from_cdn += body->size();
+        memo->shared_hits++;
+        memo->shared_bytes += body->size();
+        return out;
+      }
+    }
+  }
+  // whatever happens below, the fetches waiting for this entry are released
+  struct MemoDone {
+    RunMemo* m;
+    const RunMemo::Key& key;
+    std::shared_ptr<const Bytes> body;
+    ~MemoDone() {
+      if (!m) return;
+      std::lock_guard<std::mutex> g(m->mu);
+      RunMemo::Ent& e = m->runs[key];
+      if (body && m->kept + body->size() <= m->cap) {
+        m->kept += body->size();
+        e.body = std::move(body);
+      }
+      e.done = true;
+      m->cv.notify_all();
+    }
+  } memo_done{memo_owner ? memo : nullptr, memo_key, nullptr};
   trace::Span span("cdn", "fetch " + hex.substr(0, 12));
   const size_t want = size_t(fi->url_range.end - fi->url_range.start + 1);
   Bytes body;
@@ -135,6 +181,7 @@ XorbFetchResult XetBridge::fetch_term(const cas::Term& term, const cas::Reconstr
     run = body.data();
     run_len = body.size();
   }
+  if (memo_done.m) memo_done.body = std::make_shared<const Bytes>(run, run + run_len);
   span.arg("\"bytes\":" + std::to_string(run_len));
   stats_.xorbs_from_cdn++;
   stats_.bytes_from_cdn += run_len;

@@ -8,12 +8,15 @@
 #pragma once
 
 #include <atomic>
+#include <condition_variable>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <optional>
 #include <ostream>
 #include <functional>
 #include <string>
+#include <tuple>
 
 #include "config.h"
 #include "hub.h"
@@ -31,6 +34,31 @@ struct FetchStats {
 // Resumed: restored from a .zest-resume sidecar (bytes written by an earlier, interrupted run).
 enum class Source { Cache, Peer, Cdn, Resumed };
 
+// CDN runs shared among the term fetches of one call.  The CAS answers with one fetch entry per
+// maximal union of a file's chunk ranges in an xorb, and a term fetch downloads its whole covering
+// entry: terms that are apart in the file but neighbours in the xorb (the changed regions of a new
+// revision) would each download the same entry, which only the disk xorb cache deduplicates, and
+// only when it is on and the fetches do not race.  With a RunMemo in its options, the first fetch
+// of an entry keeps a copy here and the others wait for it and copy from it (at most `cap` bytes
+// are kept; past that, entries are downloaded again).  Costs, for the caller to weigh: the
+// downloading fetch makes one more host copy of a shared entry, and a waiting fetch holds its thread
+// until that download ends.  XetStats counts a term served from a shared run under the CDN like the
+// download itself (bytes_from_cdn is then bytes served to terms, not bytes on the wire); the memo's
+// own shared_hits / shared_bytes say how much of that never crossed the network.
+struct RunMemo {
+  // (xorb hex, entry's chunk range, entry's byte range)
+  using Key = std::tuple<std::string, uint64_t, uint64_t, uint64_t, uint64_t>;
+  struct Ent {
+    bool done = false;
+    std::shared_ptr<const Bytes> body;  // null once done: not kept (failed, or over the cap)
+  };
+  std::mutex mu;
+  std::condition_variable cv;
+  std::map<Key, Ent> runs;
+  uint64_t kept = 0, cap = uint64_t(1) << 30;
+  std::atomic<uint64_t> shared_hits{0}, shared_bytes{0};
+};
+
 struct FetchOptions {
   bool allow_p2p = true;
   bool allow_cache = true;
@@ -41,6 +69,8 @@ struct FetchOptions {
   // made by the writer's copy threads instead of this thread; on_copied() runs once they have it
   // (XorbFetchResult::copy_deferred says whether it will run).  The caller keeps the sink memory.
   std::function<void()> on_copied;
+  // Share CDN runs with the other term fetches that carry the same memo (see RunMemo).
+  std::shared_ptr<RunMemo> share;
 };
 
 struct XorbFetchResult {

@@ -123,7 +123,8 @@ size_t SettleBook::settle_all(XetBridge& bridge, bool ok) {
 
 std::vector<TermJobResult> fetch_terms_host(XetBridge& bridge, ReconCache& recs, SettleBook& book,
                                             const std::vector<TermJob>& jobs, uint8_t* hashes, int threads,
-                                            bool repair) {
+                                            bool repair, bool share_runs) {
+  const std::shared_ptr<RunMemo> share = share_runs ? std::make_shared<RunMemo>() : nullptr;
   // Flatten the jobs into (job, term, output offset, chunk index) work items.
   struct Item {
     size_t job;
@@ -218,7 +219,7 @@ std::vector<TermJobResult> fetch_terms_host(XetBridge& bridge, ReconCache& recs,
       Source src = Source::Cdn;
       std::string peer;
       try {
-        do_term(items[i], FetchOptions{true, true, repair}, &src, &peer);
+        do_term(items[i], FetchOptions{true, true, repair, {}, share}, &src, &peer);
       } catch (const std::exception& e) {
         ZTRACE("download", "term " << items[i].term << " failed (" << e.what() << "), CDN retry");
         if (src == Source::Peer && !peer.empty() && bridge.swarm()) bridge.swarm()->report_bad_peer(peer);

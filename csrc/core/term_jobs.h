@@ -95,10 +95,11 @@ std::vector<uint8_t> cached_terms(const storage::XorbCache& cache, const std::ve
 // every chunk on the CPU, write the bytes at job.dst (host memory) and the keyed-BLAKE3 chunk hashes
 // at hashes + 32 * chunk index.  A term whose copy does not decode is refetched from the CDN once
 // (its peer/cache run rejected); `repair` fetches everything from the CDN, replacing cached runs.
-// Throws on a term that fails from every source.
+// Throws on a term that fails from every source.  `share_runs`: terms of the call that lie in one
+// CAS fetch entry download it once (RunMemo, bridge.h).
 std::vector<TermJobResult> fetch_terms_host(XetBridge& bridge, ReconCache& recs, SettleBook& book,
                                             const std::vector<TermJob>& jobs, uint8_t* hashes, int threads,
-                                            bool repair);
+                                            bool repair, bool share_runs = false);
 
 // [lo, hi) byte ranges covering the runs (at[i], len[i]) of a staging slot, in address order, with
 // neighbours whose gap is at most max_gap merged (one copy command instead of two); empty runs are

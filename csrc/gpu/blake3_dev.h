@@ -169,8 +169,22 @@ __device__ __forceinline__ void fetch17(const uint32_t* w, uint32_t r[17]) {
 // One <= 1 KiB BLAKE3 chunk like hash_chunk, with block b+1's loads in flight while block b
 // compresses (the lane's 1 KiB is read as 16 x 64 B; a shift of k bytes realigns every word with
 // v_alignbyte, which is the identity for k == 0, so there is no aligned/unaligned branch).
-__device__ __forceinline__ void hash_leaf(const uint8_t* p, uint32_t len, uint64_t counter, const Key8& key,
-                                          uint32_t mode_flags, bool is_root, uint32_t cv[8]) {
+// kExact: no dword at or past `lim` is loaded (it reads as zero and is masked off anyway), for
+// messages with no readable padding behind them.
+template <bool kExact>
+__device__ __forceinline__ void fetch17_to(const uint32_t* w, const uint32_t* lim, uint32_t r[17]) {
+  if (!kExact || w + 17 <= lim) {
+    fetch17(w, r);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 17; ++i) r[i] = w + i < lim ? ((gw_t)w)[i] : 0u;
+  }
+}
+
+template <bool kExact>
+__device__ __forceinline__ void hash_leaf_to(const uint8_t* p, uint32_t len, uint64_t counter, const Key8& key,
+                                             uint32_t mode_flags, bool is_root, uint32_t cv[8],
+                                             const uint32_t* lim) {
   load_key(cv, key);
   const uint32_t nblk = len == 0 ? 1 : (len + 63) >> 6;
   const uintptr_t a = reinterpret_cast<uintptr_t>(p);
@@ -178,14 +192,14 @@ __device__ __forceinline__ void hash_leaf(const uint8_t* p, uint32_t len, uint64
   const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
   uint32_t cur[17];
   if (len) {
-    fetch17(w, cur);
+    fetch17_to<kExact>(w, lim, cur);
   } else {
 #pragma unroll
     for (int i = 0; i < 17; ++i) cur[i] = 0;
   }
   for (uint32_t b = 0; b < nblk; ++b) {
     uint32_t nxt[17];
-    if (b + 1 < nblk) fetch17(w + 16 * (b + 1), nxt);
+    if (b + 1 < nblk) fetch17_to<kExact>(w + 16 * (b + 1), lim, nxt);
     uint32_t m[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) m[i] = __builtin_amdgcn_alignbyte(cur[i + 1], cur[i], k);
@@ -208,6 +222,19 @@ __device__ __forceinline__ void hash_leaf(const uint8_t* p, uint32_t len, uint64
 #pragma unroll
     for (int i = 0; i < 17; ++i) cur[i] = nxt[i];
   }
+}
+
+__device__ __forceinline__ void hash_leaf(const uint8_t* p, uint32_t len, uint64_t counter, const Key8& key,
+                                          uint32_t mode_flags, bool is_root, uint32_t cv[8]) {
+  hash_leaf_to<false>(p, len, counter, key, mode_flags, is_root, cv, nullptr);
+}
+
+// hash_leaf for a leaf of a message that ends at `lim` (its end rounded up to a dword): the loads
+// never reach past the aligned dwords that hold a byte of the message.
+__device__ __forceinline__ void hash_leaf_exact(const uint8_t* p, uint32_t len, uint64_t counter, const Key8& key,
+                                                uint32_t mode_flags, bool is_root, uint32_t cv[8],
+                                                const uint32_t* lim) {
+  hash_leaf_to<true>(p, len, counter, key, mode_flags, is_root, cv, lim);
 }
 
 __device__ __forceinline__ void parent_cv(const uint32_t l[8], const uint32_t r[8], const Key8& key,

@@ -69,6 +69,16 @@ __host__ __device__ inline Layout layout(uint8_t* s, int n, uint32_t cap) {
   return l;
 }
 
+// Row of the caller's hash / size tables that chunk c of a launch writes: a source's rows() gives
+// the mapping to both kernels that write rows (k_hash_leaves, k_hash_tree).
+struct IdentIdx {
+  __device__ __forceinline__ uint32_t operator()(int c) const { return uint32_t(c); }
+};
+struct ReuseIdx {
+  const ZgReuse* recs;
+  __device__ __forceinline__ uint32_t operator()(int c) const { return recs[c].index; }
+};
+
 // Descriptor sources: the bytes + length of message c, or bad (hashed as described per source).
 struct ChunkSrc {  // placed Xet chunks (k_hash_chunks semantics: a bad descriptor hashes as empty)
   const ZgChunk* chunks;
@@ -76,6 +86,8 @@ struct ChunkSrc {  // placed Xet chunks (k_hash_chunks semantics: a bad descript
   uint64_t dst_n;
   static constexpr bool kBadIsFF = false;
   static constexpr bool kPlace = false;
+  static constexpr bool kReuse = false;
+  __host__ __device__ IdentIdx rows() const { return {}; }
   __device__ __forceinline__ void get(int c, const uint8_t*& p, uint32_t& len, bool& bad) const {
     uint64_t off = chunks[c].dst;
     len = chunks[c].ulen;
@@ -91,6 +103,8 @@ struct RangeSrc {  // raw (offset, len) messages (k_hash_ranges semantics: > 128
   const uint8_t* buf;
   static constexpr bool kBadIsFF = true;
   static constexpr bool kPlace = false;
+  static constexpr bool kReuse = false;
+  __host__ __device__ IdentIdx rows() const { return {}; }
   __device__ __forceinline__ void get(int c, const uint8_t*& p, uint32_t& len, bool& bad) const {
     uint64_t off = offs[c];
     len = lens[c];
@@ -125,6 +139,8 @@ struct PlaceSrc {
   int skip_compressed = 0;  // the LZ4 decoder already hashed the compressed chunks (zg_lz4_decode_ingest)
   static constexpr bool kBadIsFF = false;
   static constexpr bool kPlace = true;
+  static constexpr bool kReuse = false;
+  __host__ __device__ IdentIdx rows() const { return {}; }
   __device__ __forceinline__ bool raw_ok(const ZgChunk& ch) const {
     return ch.src + ch.ulen <= src_n && ch.dst + ch.ulen <= dst_n && ch.ulen <= kMaxChunk;
   }
@@ -146,10 +162,41 @@ struct PlaceSrc {
   }
 };
 
+// K12 (zg_reuse_chunks): a gather fused with the chunk hash.  Record c's bytes sit at an absolute
+// device address of any alignment (a chunk of another revision's file buffer, one torch allocation
+// per file, so there is no common base and nothing to bounds-check against: the host wrapper
+// vouches for every record).  The leaf waves copy them to dst + rec.dst like the fused ingest does
+// (wave_copy: aligned 16-byte stores, source dwords funnel-shifted) and hash them from the source
+// lines the copy just pulled on chip, so HBM is read once and written once.  Hash and size go to row
+// rec.index of the caller's tables (the chunk's place in the new file's leaf table, in any order);
+// rows no record names are not touched.  Source loads stay inside the aligned dwords that hold a
+// byte of the chunk (wave_copy by construction, the hash through hash_leaf_exact), so a chunk may
+// end at the last byte of its allocation.  A record over 128 KiB (refused on the host) is not
+// copied and hashes as empty.
+struct ReuseSrc {
+  const ZgReuse* recs;
+  uint8_t* dst;
+  static constexpr bool kBadIsFF = false;
+  static constexpr bool kPlace = true;
+  static constexpr bool kReuse = true;
+  __host__ __device__ ReuseIdx rows() const { return {recs}; }
+  __device__ __forceinline__ void get(int c, const uint8_t*& p, uint32_t& len, bool& bad) const {
+    const ZgReuse r = recs[c];
+    len = r.len;
+    bad = len > kMaxChunk;
+    if (bad) len = 0;
+    p = reinterpret_cast<const uint8_t*>(uintptr_t(r.src));
+  }
+  __device__ __forceinline__ void report(int) const {}
+};
+
 template <class Src>
 __device__ __forceinline__ uint32_t n_leaves(const Src& s, int c) {
   uint32_t len;
-  if constexpr (Src::kPlace) {
+  if constexpr (Src::kReuse) {
+    len = s.recs[c].len;
+    if (len > kMaxChunk) len = 0;
+  } else if constexpr (Src::kPlace) {
     // the plan needs only the size: one 4-byte load instead of the 32-byte record.  A record that later fails its bounds check in get() hashes
     // as empty leaves, so its chunk hash -- and the file's Merkle check -- fails as it should.
     len = s.chunks[c].ulen;
@@ -259,6 +306,23 @@ __device__ __forceinline__ void place_task(const PlaceSrc& s, const Layout& l, u
   }
 }
 
+// K12's copy: the bytes of the task's leaves go from each record's own address to dst + rec.dst.
+__device__ __forceinline__ void place_task(const ReuseSrc& s, const Layout& l, uint32_t task, int lo_c, int hi_c,
+                                           uint32_t lane) {
+  const uint32_t g0 = task * kWave, g1 = g0 + kWave;
+  for (int c = lo_c; c <= hi_c; ++c) {
+    const ZgReuse r = s.recs[c];
+    const uint32_t len = __builtin_amdgcn_readfirstlane(r.len);
+    if (len == 0 || len > kMaxChunk) continue;
+    const uint32_t p0 = __builtin_amdgcn_readfirstlane(l.P[c]), p1 = __builtin_amdgcn_readfirstlane(l.P[c + 1]);
+    const uint32_t a = max(p0, g0) - p0, b = min(p1, g1) - p0;  // leaf range of this chunk in the task
+    if (a >= b) continue;
+    const uint64_t lo = uint64_t(a) << 10, hi = min(uint64_t(b) << 10, uint64_t(len));
+    if (lo < hi)
+      zwv::wave_copy(s.dst + r.dst + lo, reinterpret_cast<const uint8_t*>(uintptr_t(r.src)) + lo, hi - lo, lane);
+  }
+}
+
 template <class Src>
 __global__ void __launch_bounds__(256) k_hash_leaves(Src s, int n, int key_mode, uint8_t* scratch, uint32_t cap,
                                                      uint8_t* __restrict__ out, uint64_t* __restrict__ sizes) {
@@ -295,17 +359,25 @@ __global__ void __launch_bounds__(256) k_hash_leaves(Src s, int n, int key_mode,
     if constexpr (Src::kPlace) {
       if (bad && b == 0) s.report(c);  // one report per bad descriptor (its first leaf's lane)
     }
-    zg::hash_leaf(p + (uint64_t(b) << 10), seg, b, key, mode, nb == 1, cv);
+    if constexpr (Src::kReuse) {
+      // loads end with the last aligned dword that holds a byte of the chunk
+      const uintptr_t end = (reinterpret_cast<uintptr_t>(p) + len + 3) & ~uintptr_t(3);
+      zg::hash_leaf_exact(p + (uint64_t(b) << 10), seg, b, key, mode, nb == 1, cv,
+                          reinterpret_cast<const uint32_t*>(end));
+    } else {
+      zg::hash_leaf(p + (uint64_t(b) << 10), seg, b, key, mode, nb == 1, cv);
+    }
+    const uint64_t row = s.rows()(c);
     if (nb == 1) {
       if (Src::kBadIsFF && bad) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) cv[i] = 0xFFFFFFFFu;
       }
-      store8(reinterpret_cast<uint32_t*>(out + 32 * uint64_t(c)), cv);
+      store8(reinterpret_cast<uint32_t*>(out + 32 * row), cv);
     } else {
       store8(l.CV + 8 * uint64_t(g), cv);
     }
-    if (sizes && b == 0) sizes[c] = len;
+    if (sizes && b == 0) sizes[row] = len;
   }
 }
 
@@ -313,15 +385,17 @@ __global__ void __launch_bounds__(256) k_hash_leaves(Src s, int n, int key_mode,
 // (an LDS copy of the group's CVs was slower: 32 KiB per wave cut residency to 5 waves per CU, and
 // this kernel is latency-bound).  Level s+1 reads what level s stored: a workgroup-scope
 // release/acquire between levels orders them (one CU, so its vector L1 sees the wave's own stores).
+template <class Idx>
 __global__ void __launch_bounds__(256) k_hash_tree(int n, int key_mode, uint8_t* scratch, uint32_t cap,
-                                                   uint8_t* __restrict__ out) {
+                                                   uint8_t* __restrict__ out, Idx row) {
   const Layout l = layout(scratch, n, cap);
   const PlanHdr* h = reinterpret_cast<const PlanHdr*>(scratch);
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const int c0 = __builtin_amdgcn_readfirstlane((blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6)) * kTreeG);
   if (c0 >= n) return;
   if (__builtin_amdgcn_readfirstlane(h->overflow)) {  // undersized scratch: nothing verifies
-    if (c0 + int(lane >> 3) < n) reinterpret_cast<uint32_t*>(out + 32 * uint64_t(c0))[lane] = 0xFFFFFFFFu;
+    const int c = c0 + int(lane >> 3);
+    if (c < n) reinterpret_cast<uint32_t*>(out + 32 * uint64_t(row(c)))[lane & 7] = 0xFFFFFFFFu;
     return;
   }
   const zg::Key8& key = key_of(key_mode);
@@ -363,7 +437,7 @@ __global__ void __launch_bounds__(256) k_hash_tree(int n, int key_mode, uint8_t*
 #pragma unroll
           for (int k = 0; k < 8; ++k) o[k] = lft[k];
         }
-        if (mi == 2) store8(reinterpret_cast<uint32_t*>(out + 32 * uint64_t(c0 + ci)), o);
+        if (mi == 2) store8(reinterpret_cast<uint32_t*>(out + 32 * uint64_t(row(c0 + ci))), o);
         else store8(nodes + 8 * j, o);
       }
     }
@@ -397,7 +471,8 @@ hipError_t launch_flat(Src s, int n, int key_mode, uint8_t* out, uint64_t* sizes
   hipLaunchKernelGGL((k_hash_leaves<Src>), dim3((waves + 3) / 4), dim3(256), 0, stream, s, n, key_mode, scratch, cap,
                      out, sizes);
   const int groups = (n + kTreeG - 1) / kTreeG;
-  hipLaunchKernelGGL(k_hash_tree, dim3((groups + 3) / 4), dim3(256), 0, stream, n, key_mode, scratch, cap, out);
+  hipLaunchKernelGGL((k_hash_tree<decltype(s.rows())>), dim3((groups + 3) / 4), dim3(256), 0, stream, n, key_mode,
+                     scratch, cap, out, s.rows());
   return hipGetLastError();
 }
 
@@ -441,6 +516,11 @@ hipError_t zg_hash_ranges_flat(const uint8_t* buf, const uint64_t* offsets, cons
                                uint8_t* hashes, int key_mode, uint8_t* scratch, size_t scratch_bytes,
                                hipStream_t stream) {
   return launch_flat(RangeSrc{offsets, lens, buf}, n, key_mode, hashes, nullptr, scratch, scratch_bytes, stream);
+}
+
+hipError_t zg_reuse_chunks(const ZgReuse* recs, int n, uint8_t* dst, uint8_t* hashes, uint64_t* sizes,
+                           uint8_t* scratch, size_t scratch_bytes, hipStream_t stream) {
+  return launch_flat(ReuseSrc{recs, dst}, n, 0, hashes, sizes, scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

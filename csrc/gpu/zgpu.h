@@ -225,6 +225,24 @@ typedef struct ZgSliceSrcs {
 hipError_t zg_slice_gather_peers(const ZgSliceSrcs* srcs, const uint64_t* table, uint32_t n, uint64_t dst_total,
                                  uint8_t* dst, uint32_t max_blocks, hipStream_t stream);
 
+// K12 (blake3_flat.hip): reuse chunks that are resident on this device under another revision.
+// Record i copies `len` bytes from the absolute device address `src` (any alignment, any allocation)
+// to dst + `dst`, writes their Xet chunk hash (keyed, DATA_KEY) to hashes + 32 * `index` and, when
+// sizes is non-null, `len` to sizes[`index`].  Rows of hashes / sizes that no record names keep their
+// bytes, and no byte of dst outside the records' outputs is written.  len == 0 is legal (the empty
+// hash, nothing copied); len > 128 KiB must be refused by the caller (such a record is not copied and
+// hashes as empty).  Source loads are widened at most to the aligned dwords that hold a byte of the
+// chunk.  scratch: zg_hash_scratch_bytes(n, sum of len) of device memory, one per concurrently
+// running launch.  The caller vouches for every record: nothing is checked on the device.
+typedef struct ZgReuse {
+  uint64_t src;    // device address of the chunk's bytes
+  uint64_t dst;    // output offset in dst
+  uint32_t len;    // bytes (<= 128 KiB)
+  uint32_t index;  // row of hashes / sizes
+} ZgReuse;
+hipError_t zg_reuse_chunks(const ZgReuse* recs, int n, uint8_t* dst, uint8_t* hashes, uint64_t* sizes,
+                           uint8_t* scratch, size_t scratch_bytes, hipStream_t stream);
+
 int zg_device_count(void);
 // K6: out[i] (20 B) = SHA1("zest-xet-v1:" || hashes[i] (32 B)); out must be 4-byte aligned.
 hipError_t zg_sha1_info_hash(const uint8_t* hashes, int n, uint8_t* out, hipStream_t stream);

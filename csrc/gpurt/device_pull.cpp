@@ -306,7 +306,7 @@ struct DeviceXetPull::Impl {
   // the runs behind the terms stay in book_ until settle(file).  A range whose fetched runs do not
   // match its plan, or any decode error of the call, is refetched once from the CDN.
   std::vector<TermJobResult> pull_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, uint64_t* sizes,
-                                        bool repair) {
+                                        bool repair, bool share_runs) {
     init_device();
     hip_check(hipSetDevice(device_), "hipSetDevice");
     const std::vector<Seg> segs = segs_of_jobs(jobs);
@@ -317,6 +317,7 @@ struct DeviceXetPull::Impl {
       FetchOptions opt;
       opt.repair = repair || attempt > 0;
       if (attempt > 0) opt.allow_cache = opt.allow_p2p = false;
+      if (share_runs) opt.share = std::make_shared<RunMemo>();  // one memo per attempt
       // a retry covers a subset: its chunk indices are no longer consecutive, so run it seg by seg
       std::vector<std::vector<size_t>> groups;
       if (attempt == 0) groups.push_back(todo);
@@ -1465,8 +1466,8 @@ std::vector<PullFileStats> DeviceXetPull::pull_files(const std::vector<PullReque
 }
 
 std::vector<TermJobResult> DeviceXetPull::pull_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, uint64_t* sizes,
-                                                     bool repair) {
-  return impl_->pull_terms(jobs, hashes, sizes, repair);
+                                                     bool repair, bool share_runs) {
+  return impl_->pull_terms(jobs, hashes, sizes, repair, share_runs);
 }
 uint64_t DeviceXetPull::submit_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, uint64_t* sizes) {
   return impl_->submit_terms(jobs, hashes, sizes);

@@ -68,8 +68,9 @@ class DeviceXetPull {
   // each job's device address, chunk hashes / sizes into hashes[32 * i] / sizes[i] (device tables,
   // i = the job's chunk0 + chunk index).  Jobs must cover consecutive chunk indices.  No Merkle
   // check: the caller verifies each whole file, then settle(file, ok) publishes or drops the runs.
+  // share_runs: terms of the call that lie in one CAS fetch entry download it once (RunMemo, bridge.h).
   std::vector<TermJobResult> pull_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, uint64_t* sizes,
-                                        bool repair = false);
+                                        bool repair = false, bool share_runs = false);
   // Streaming form of pull_terms (the swarm pull's rounds): the jobs become one item of a continuous
   // pipeline that persists across items (no stream drain between them); returns a ticket at once.
   uint64_t submit_terms(const std::vector<TermJob>& jobs, uint8_t* hashes, uint64_t* sizes);

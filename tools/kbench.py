@@ -475,6 +475,53 @@ def main():
             del out11, got11
         del out, flat, tab_d, views, got
 
+    if want("reuse_chunks"):
+        # K12 reuse_chunks: 1 GiB of CDC-sized chunks (the size mix of 64 MiB of the arena's own bytes,
+        # repeated) at random source and destination misalignments, next to the two passes it fuses, built
+        # from what existed before it: K1 over the source (leaf-flat) plus a device copy of as many
+        # bytes.  K12 moves 2 bytes per byte (one read, one write), the two passes 3.  Alternated, three
+        # rounds; the spread between rounds is the noise to read the difference against.
+        rng = np.random.default_rng(12)
+        ends = np.asarray(C.chunk_ends(arena[: min(n, 64 << 20)].cpu().numpy().tobytes()), dtype=np.int64)
+        mix = np.diff(np.concatenate([[0], ends]))
+        ln = np.tile(mix, -(-(1 << 30) // int(mix.sum())))
+        ln = ln[: int(np.searchsorted(np.cumsum(ln), 1 << 30)) + 1]
+        m, nb = len(ln), int(ln.sum())
+        gap_s, gap_d = rng.integers(0, 16, m), rng.integers(0, 16, m)
+        s_off = np.cumsum(ln + gap_s) - ln
+        d_off = np.cumsum(ln + gap_d) - ln
+        src12 = ops.padded_empty(int(s_off[-1] + ln[-1]), dev)
+        ops.fill_synthetic(src12, 3, 0, 0)
+        dst12 = ops.padded_empty(int(d_off[-1] + ln[-1]), dev)
+        flat12 = ops.padded_empty(nb, dev)
+        h12 = torch.zeros((m, 32), dtype=torch.uint8, device=dev)
+        h2p = torch.zeros((m, 32), dtype=torch.uint8, device=dev)
+        sz12 = torch.zeros(m, dtype=torch.int64, device=dev)
+        rec = np.empty(m, dtype=ops.REUSE_DTYPE)
+        rec["src"], rec["dst"], rec["len"], rec["index"] = src12.data_ptr() + s_off, d_off, ln, rng.permutation(m)
+        rec_d = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        o_d = torch.from_numpy(s_off.astype(np.int64)).to(dev)
+        l_d = torch.from_numpy(ln.astype(np.uint32).view(np.int32)).to(dev)
+        sp, sb = ops.HashScratch(dev).get(m, nb)  # (`hs` above is rebound by the sha1 / merkle rows)
+
+        def two_pass():
+            H.hash_ranges(src12.data_ptr(), o_d.data_ptr(), l_d.data_ptr(), m, h2p.data_ptr(), 0, st, sp, sb)
+            flat12.copy_(src12[:nb])
+
+        rows12 = (("reuse_chunks[kernel]", lambda: H.reuse_chunks(rec_d.data_ptr(), m, dst12.data_ptr(), h12.data_ptr(),
+                                                                  sz12.data_ptr(), sp, sb, st)),
+                  ("reuse_two_pass[hash_ranges+copy]", two_pass),
+                  ("reuse_chunks[ops]", lambda: ops.reuse_chunks(rec["src"], ln, dst12, d_off, h12, rec["index"], sz12,
+                                                                 buffers=[src12])))
+        for rnd in range(3):
+            for name, fn in rows12:
+                ms = timed(fn, a.iters)
+                emit(kernel=name, round=rnd, bytes=nb, ms=ms, gbps=nb / ms / 1e6, chunks=m)
+        assert torch.equal(h12[torch.from_numpy(rec["index"].astype(np.int64)).to(dev)], h2p)  # same hashes, at their rows
+        k = m // 2
+        assert torch.equal(dst12[int(d_off[k]):int(d_off[k] + ln[k])], src12[int(s_off[k]):int(s_off[k] + ln[k])])
+        del src12, dst12, flat12, rec_d
+
     if want("h2d"):
         pin = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()
         d = torch.empty(1 << 30, dtype=torch.uint8, device=dev)

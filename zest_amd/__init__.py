@@ -58,7 +58,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
          group=None, repo_type: str = "model", verbose: bool = False, direct: bool | None = None,
          save_snapshot: bool = False, threads: int = 16, staging_bytes: int = 1 << 30, stats: dict | None = None,
          exchange: str = "auto", round_bytes: int | None = None, seed=False, shard=None,
-         scratch_bytes: int | None = None):
+         scratch_bytes: int | None = None, base=None):
     """Download `repo@revision` via zest.
 
     * default: returns the HF-cache snapshot directory (reference behaviour).
@@ -92,6 +92,17 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       bounds device memory, not network bytes.  Files in which the rank keeps nothing (per
       model.safetensors.index.json) are not fetched.  `stats["shard"]` receives file_bytes, kept_bytes,
       skipped_files, groups, scratch_bytes and gather_s.
+    * base=w0 (the Weights an earlier direct pull returned, its `.resident` set, or a list of those),
+      device="cuda:N" / "cpu" direct pulls: a delta pull.  Reconstruction terms of the new revision
+      whose chunks are all resident in the base's memory on the same device are copied from there and
+      re-hashed on the way (ops.reuse_chunks, kernel K12) instead of fetched; the rest takes the usual
+      waterfall.  Every file is verified from the hashes of the bytes in its new buffer, so nothing
+      about the base is trusted: a file that misses (base tensors modified in place) has its reused
+      terms fetched from the network and is checked again.  The base is not updated in place: old and
+      new weights coexist until the caller drops the old ones.  seed=True serves the new revision from
+      HBM as usual.  `stats["delta"]` receives reused_terms, fetched_terms, reused_bytes, fetched_bytes,
+      reused_files, refetched_terms, reuse_s, fetch_s and verify_s.  Refused with device="all", shard=,
+      direct=False, no device, and a base on another device (zest_amd.delta).
     * shard= with device="all": the collective sharded pull over `group` (default WORLD; start one
       process per GPU and call zest_amd.parallel.init_from_env() first).  The shard's rank and world
       must be the group's.  Each file is fetched and verified whole by one owner rank and every rank
@@ -102,6 +113,19 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       every kept byte.  `stats["shard"]` also receives exchange, rounds, owned_files, fetched_bytes,
       received_bytes and p2p_ratio.  seed=, save_snapshot=True and direct=False stay refused.
     """
+    if base is not None:
+        if device is None and not as_tensors:
+            raise ValueError("base= needs a device pull: a snapshot pull lands on disk, where nothing is resident; use "
+                             "device='cuda:N' (or 'cpu'), the device the base was pulled to")
+        if device == "all":
+            raise ValueError("base= is not supported with device='all' (swarm pulls): run the delta pull per GPU with "
+                             "device='cuda:N' and that GPU's own base")
+        if shard is not None:
+            raise ValueError("base= is not supported with shard=: a sharded pull keeps no whole file resident to reuse "
+                             "or to serve as the next base; use an unsharded pull")
+        if direct is False:
+            raise ValueError("base= is not supported with direct=False (the snapshot path): resident chunks are "
+                             "copied into the buffers of a device-direct pull; leave direct at its default")
     if shard is not None:
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu'); a snapshot pull has no tensors "
@@ -160,7 +184,8 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
         return pull_to_device(repo, revision, device or "cuda:0", p2p=p2p, peers=peers, tracker=tracker, dht=dht,
                               dht_bootstrap=dht_bootstrap, repo_type=repo_type, save_snapshot=save_snapshot,
                               threads=threads, staging_bytes=staging_bytes, include=include, seed=seed, shard=shard,
-                              scratch_bytes=scratch_bytes, stats=stats if shard is not None else None)
+                              scratch_bytes=scratch_bytes,
+                              stats=stats if shard is not None or base is not None else None, base=base)
     from .device import load_snapshot
 
     res = _client.pull_detailed(repo, revision, **kw)

@@ -36,6 +36,32 @@ class VerifyError(RuntimeError):
     pass
 
 
+class Weights(dict):
+    """The tensors of a direct pull, `{name: tensor}`: a dict in every respect (equality, iteration,
+    pickling of its items), plus `.resident`, the `zest_amd.delta.ResidentSet` of the Xet files the
+    tensors are views of.  `pull(repo, new_revision, device=..., base=weights)` copies the chunks the
+    new revision shares with them out of this memory instead of fetching them.  The set is built on
+    first use from what the pull already had (file buffers, chunk sizes, reconstruction terms): no
+    request, no device memory.  It keeps the file buffers alive as long as it is referenced."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self._files = []  # (buffer, chunk_lens, term_keys) per Xet file
+        self._device = None
+        self._resident = None
+
+    def _set_files(self, files, device) -> None:
+        self._files, self._device, self._resident = list(files), torch.device(device), None
+
+    @property
+    def resident(self):
+        if self._resident is None and self._device is not None:
+            from .delta import ResidentSet
+
+            self._resident = ResidentSet.from_files(self._files, self._device)
+        return self._resident
+
+
 def parse_safetensors_header(head: bytes) -> tuple[int, dict]:
     """Returns (data_start, metadata) from the first bytes of a .safetensors file."""
     if len(head) < 8:

@@ -44,7 +44,17 @@ from . import shard as zshard
 def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: bool = True, peers=None,
                    tracker=None, dht: bool = True, dht_bootstrap=None, repo_type: str = "model",
                    save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False,
-                   shard=None, scratch_bytes: int | None = None, stats: dict | None = None):
+                   shard=None, scratch_bytes: int | None = None, stats: dict | None = None, base=None):
+    if base is not None:
+        if device is None:
+            raise ValueError("base= needs a device: a delta pull copies resident chunks inside device='cuda:N' (or "
+                             "'cpu'); use the base's device")
+        if device == "all":
+            raise ValueError("base= is not supported with device='all' (swarm pulls): run the delta pull per GPU with "
+                             "device='cuda:N' and that GPU's own base")
+        if shard is not None:
+            raise ValueError("base= is not supported with shard=: a sharded pull keeps no whole file resident to reuse "
+                             "or to serve as the next base; use an unsharded pull")
     if shard is not None:
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu')")
@@ -72,39 +82,50 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
         seed_port = _seed_port(seed)
         if dev.type != "cuda":
             raise ValueError(f"seed= serves weights resident in GPU memory: unsupported with device={str(device)!r}")
+    rs = None
+    if base is not None:  # refusals first: nothing is listed or allocated for a base that cannot serve
+        from . import delta as zdelta
+
+        rs = zdelta.as_resident_set(base, dev)
     commit, files = _core.list_repo_files(repo, revision, repo_type)
     if include:  # file-name suffixes, as `zest pull --include` (csrc/core/pull.cpp)
         files = [f for f in files if any(f["path"].endswith(x) for x in include)]
     st_files = [f for f in files if f["path"].endswith(".safetensors")]
     xet = [f for f in st_files if f["xet_hash"]]
     plain = [f for f in st_files if not f["xet_hash"]]
-    out: dict[str, torch.Tensor] = {}
+    out = zdev.Weights()
+    resident = []  # (buffer, chunk_lens, term_keys) per Xet file: what seeding and the next delta pull need
     if xet and dev.type == "cpu":
         hf = _core.HostXetFetcher(repo, revision, repo_type, p2p, list(peers or []), tracker, dht,
                                   list(dht_bootstrap or []), threads)
-        bufs = [torch.empty(f["size"], dtype=torch.uint8) for f in xet]
-        hf.fetch_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
-        for f, buf in zip(xet, bufs):
-            _add_views(out, buf, f["path"])
-            if save_snapshot:
-                _save(repo, commit or revision, f["path"], buf)
+        if rs is not None:
+            resident = zdelta.pull_files_delta(hf, xet, dev, rs, _delta_info(stats))
+        else:
+            bufs = [torch.empty(f["size"], dtype=torch.uint8) for f in xet]
+            res = hf.fetch_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
+            resident = [(b, r["chunk_lens"], hf.term_keys(f["xet_hash"])) for f, b, r in zip(xet, bufs, res)]
     elif xet:
         dp = ops.hip().DeviceXetPull(repo, revision, repo_type, p2p, list(peers or []), tracker, dht,
                                      list(dht_bootstrap or []), dev.index or 0, staging_bytes, threads)
-        bufs = [ops.padded_empty(f["size"], dev)[:f["size"]] for f in xet]
-        torch.cuda.synchronize(dev)  # allocations visible to the pull's private stream
-        # one pipeline for all files: staging batches cross file boundaries
-        stats = dp.pull_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
+        if rs is not None:
+            with torch.cuda.device(dev):
+                resident = zdelta.pull_files_delta(dp, xet, dev, rs, _delta_info(stats))
+        else:
+            bufs = [ops.padded_empty(f["size"], dev)[:f["size"]] for f in xet]
+            torch.cuda.synchronize(dev)  # allocations visible to the pull's private stream
+            # one pipeline for all files: staging batches cross file boundaries
+            res = dp.pull_files([(f["xet_hash"], b.data_ptr(), f["size"]) for f, b in zip(xet, bufs)])
+            # the reconstructions are cached by the pull: listing their terms costs no request
+            resident = [(b, r["chunk_lens"], dp.term_keys(f["xet_hash"])) for f, b, r in zip(xet, bufs, res)]
         if seed_port is not None:  # the files verified: serve their xorbs from where they now live
             from . import seed as zseed
 
-            zseed._active.append(zseed.ResidentSeedServer(
-                [(b, st["chunk_lens"], dp.term_keys(f["xet_hash"])) for f, b, st in zip(xet, bufs, stats)],
-                dev, seed_port))
-        for f, buf in zip(xet, bufs):
-            _add_views(out, buf, f["path"])
-            if save_snapshot:
-                _save(repo, commit or revision, f["path"], buf)
+            zseed._active.append(zseed.ResidentSeedServer(resident, dev, seed_port))
+    for f, (buf, _, _) in zip(xet, resident):
+        _add_views(out, buf, f["path"])
+        if save_snapshot:
+            _save(repo, commit or revision, f["path"], buf)
+    out._set_files(resident, dev)
     if plain or save_snapshot:
         inc = [f["path"] for f in plain] + ([f["path"] for f in files if not f["path"].endswith(".safetensors")]
                                            if save_snapshot else [])
@@ -115,6 +136,14 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
                 buf = zdev.load_file(os.path.join(r["snapshot_dir"], f["path"]), dev)
                 _add_views(out, buf, f["path"])
     return out
+
+
+def _delta_info(stats: dict | None) -> dict:
+    """The dict that receives a delta pull's counters: stats["delta"] when the caller passed stats."""
+    info: dict = {}
+    if stats is not None:
+        stats["delta"] = info
+    return info
 
 
 DEFAULT_SCRATCH = 16 << 30  # a default to revisit with measurements, not a tuned value

@@ -6,7 +6,8 @@ bad descriptor can never become an out-of-bounds GPU access.  GPU tensors always
 CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/CPU tests use.
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
-K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers.
+K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers,
+K12 reuse_chunks.
 """
 from __future__ import annotations
 
@@ -768,6 +769,148 @@ def _slice_gather_cpu(src: np.ndarray, table: np.ndarray, dst: np.ndarray) -> No
             continue
         runs = np.lib.stride_tricks.as_strided(src[so:], shape=(nr, rb), strides=(st, 1), writeable=False)
         dst[do:do + rb * nr].reshape(nr, rb)[...] = runs
+
+
+# ----------------------------------------------------------------------------------------------
+# K12: copy + re-hash chunks that are resident on the device under another revision
+# ----------------------------------------------------------------------------------------------
+REUSE_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u4"), ("index", "<u4")])
+MAX_CHUNK = 128 * 1024
+
+
+REUSE_LAUNCH_BYTES = 1 << 30  # chunk bytes per launch: bounds the hash scratch (32 B per KiB) of a whole-model table
+
+
+def _check_reuse(src, lens, offs, index, dst_n: int, rows: int, buffers) -> None:
+    """Refuse a reuse table (ValueError naming the record) unless every chunk lies inside one of
+    `buffers`, every output inside dst, outputs are pairwise disjoint and indices unique rows.
+    src / lens / offs / index: int64-safe uint64 arrays of one length."""
+    what = "reuse_chunks: "
+
+    def first(mask):
+        return int(np.flatnonzero(mask)[0])
+
+    if (lens > MAX_CHUNK).any():
+        i = first(lens > MAX_CHUNK)
+        raise ValueError(f"{what}record {i}: len {int(lens[i])} is over the chunk maximum of {MAX_CHUNK} bytes")
+    ok = lens == 0
+    for t in buffers:  # one buffer must hold all of a chunk: neighbouring buffers do not add up
+        b0 = np.uint64(t.data_ptr())
+        b1 = np.uint64(t.data_ptr() + t.numel() * t.element_size())
+        ok |= (src >= b0) & (src <= b1) & (lens <= b1 - np.minimum(src, b1))
+    if not ok.all():
+        i = first(~ok)
+        raise ValueError(f"{what}record {i}: chunk [{int(src[i]):#x}, {int(src[i] + lens[i]):#x}) lies outside "
+                         "every buffer")
+    past = (offs > np.uint64(dst_n)) | (lens > np.uint64(dst_n) - np.minimum(offs, np.uint64(dst_n)))
+    if past.any():
+        i = first(past)
+        raise ValueError(f"{what}record {i}: output [{int(offs[i])}, {int(offs[i]) + int(lens[i])}) reaches past dst "
+                         f"({dst_n} bytes)")
+    live = np.flatnonzero(lens)
+    order = live[np.argsort(offs[live], kind="stable")]
+    clash = offs[order][1:] < (offs[order] + lens[order])[:-1]
+    if clash.any():
+        k = first(clash)
+        i, j = int(order[k + 1]), int(order[k])
+        raise ValueError(f"{what}record {i}: output [{int(offs[i])}, {int(offs[i] + lens[i])}) overlaps record {j}'s")
+    if (index >= np.uint64(rows)).any():
+        i = first(index >= np.uint64(rows))
+        raise ValueError(f"{what}record {i}: index {int(index[i])} is past the table ({rows} rows)")
+    order = np.argsort(index, kind="stable")
+    dup = index[order][1:] == index[order][:-1]
+    if dup.any():
+        k = first(dup)
+        i, j = int(order[k + 1]), int(order[k])
+        raise ValueError(f"{what}record {i}: index {int(index[i])} is also record {j}'s")
+
+
+def _u64(a, name: str) -> np.ndarray:
+    a = np.asarray(a).reshape(-1)
+    if a.dtype.kind not in "ui" and len(a):
+        raise ValueError(f"reuse_chunks: {name} must be integers")
+    if a.dtype.kind == "i" and (a < 0).any():
+        raise ValueError(f"reuse_chunks: {name} must not be negative")
+    return a.astype(np.uint64)
+
+
+def reuse_chunks(src_addrs, lens, dst: torch.Tensor, dst_offs, hashes: torch.Tensor, hash_index, sizes=None,
+                 buffers=(), stream=None) -> None:
+    """Copy chunks that already sit in this device's memory into `dst` and re-hash them on the way:
+    K12, csrc/gpu/blake3_flat.hip (zg_reuse_chunks).
+
+    Record i copies lens[i] bytes from the absolute address src_addrs[i] (any alignment) to
+    dst[dst_offs[i]:], writes their Xet chunk hash to hashes[hash_index[i]] (uint8 [N, 32]) and
+    lens[i] to sizes[hash_index[i]] (int64 [N], optional).  Rows no record names and bytes of dst
+    outside the outputs keep their values; a zero-length record writes the empty hash.  Nothing can
+    be checked on the device against absolute addresses, so a table is refused here (ValueError
+    naming the record) unless every chunk lies inside one of `buffers` (the tensors that vouch for
+    the memory, on dst's device), every output inside dst, outputs are pairwise disjoint, indices
+    are unique rows of the tables and no chunk is over 128 KiB.  GPU tensors: asynchronous on
+    `stream` (default: the current stream), one launch per REUSE_LAUNCH_BYTES of chunks, table
+    upload and scratch ordered on that stream; CPU tensors (host addresses): a NumPy path with the
+    same bytes and hashes."""
+    src, lens, offs, index = (_u64(a, k) for a, k in ((src_addrs, "src_addrs"), (lens, "lens"),
+                                                      (dst_offs, "dst_offs"), (hash_index, "hash_index")))
+    n = len(src)
+    if not (len(lens) == len(offs) == len(index) == n):
+        raise ValueError("reuse_chunks: src_addrs, lens, dst_offs and hash_index must be equally long")
+    if dst.dtype != torch.uint8 or not dst.is_contiguous():
+        raise ValueError("reuse_chunks: dst must be a contiguous uint8 tensor")
+    if hashes.dtype != torch.uint8 or hashes.dim() != 2 or hashes.shape[1] != 32 or not hashes.is_contiguous():
+        raise ValueError("reuse_chunks: hashes must be a contiguous uint8 [N, 32] tensor")
+    rows = hashes.shape[0]
+    if sizes is not None and (sizes.dtype != torch.int64 or sizes.dim() != 1 or sizes.shape[0] != rows
+                              or not sizes.is_contiguous()):
+        raise ValueError("reuse_chunks: sizes must be a contiguous int64 [N] tensor as long as hashes")
+    dev = dst.device
+    for name, t in (("hashes", hashes), ("sizes", sizes)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"reuse_chunks: {name} is on {t.device}, dst on {dev}")
+    buffers = list(buffers)
+    for k, t in enumerate(buffers):
+        if t.device != dev:
+            raise ValueError(f"reuse_chunks: buffer {k} is on {t.device}, dst on {dev}")
+    _check_reuse(src, lens, offs, index, dst.numel(), rows, buffers)
+    if n == 0:
+        return
+    if dev.type != "cuda":
+        import ctypes
+
+        d = dst.reshape(-1).numpy()
+        for a, ln, o, r in zip(src.tolist(), lens.tolist(), offs.tolist(), index.tolist()):
+            data = ctypes.string_at(a, ln) if ln else b""
+            d[o:o + ln] = np.frombuffer(data, dtype=np.uint8)
+            hashes[r] = torch.from_numpy(np.frombuffer(_core.chunk_hash(data), dtype=np.uint8).copy())
+            if sizes is not None:
+                sizes[r] = ln
+        return
+    H = hip()
+    assert H.REUSE_BYTES == REUSE_DTYPE.itemsize, "ZgReuse layout drift"
+    if hashes.data_ptr() % 16:
+        raise ValueError("reuse_chunks: hashes must be 16-byte aligned")
+    rec = np.empty(n, dtype=REUSE_DTYPE)
+    rec["src"], rec["dst"], rec["len"], rec["index"] = src, offs, lens, index
+    # launches of at most REUSE_LAUNCH_BYTES: cut where the running byte count passes a multiple of it
+    cum = np.cumsum(lens, dtype=np.uint64)
+    cuts = [0] + (np.flatnonzero(np.diff(cum // np.uint64(REUSE_LAUNCH_BYTES))) + 1).tolist() + [n]
+    parts = [(a, b, int(lens[a:b].sum(dtype=np.uint64))) for a, b in zip(cuts, cuts[1:]) if b > a]
+    sb = max(H.hash_scratch_bytes(b - a, tot) for a, b, tot in parts)
+
+    def alloc():
+        return _dev_array(rec, dev), torch.empty(sb, dtype=torch.uint8, device=dev)
+
+    if stream is None:
+        st = _stream(dev)
+        tab, scratch = alloc()
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the uploads and frees are ordered on the launch's stream
+            tab, scratch = alloc()
+    sz = sizes.data_ptr() if sizes is not None else 0
+    for a, b, _ in parts:  # one stream: the launches run in order and share the scratch
+        H.reuse_chunks(tab.data_ptr() + a * REUSE_DTYPE.itemsize, b - a, dst.data_ptr(), hashes.data_ptr(), sz,
+                       scratch.data_ptr(), sb, st)
 
 
 # ----------------------------------------------------------------------------------------------

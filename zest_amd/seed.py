@@ -145,6 +145,24 @@ class HbmCacheSeedServer:
         self.seeder.stop()
 
 
+def merge_chunk_refs(refs: dict) -> dict:
+    """`{xorb_hex: [(first_chunk, addrs, lens), ...]}` with overlapping or neighbouring references
+    -> the same map with maximal runs of consecutive chunk indices, sorted by first_chunk; a chunk
+    index referenced more than once keeps its first reference.  The merge step of
+    plan_resident_runs, also used to unite two plans (zest_amd.delta.ResidentSet)."""
+    plan = {}
+    for hx, rs in refs.items():
+        idx = np.concatenate([np.arange(c0, c0 + len(a), dtype=np.int64) for c0, a, _ in rs])
+        addrs = np.concatenate([a for _, a, _ in rs])
+        lens = np.concatenate([ln for _, _, ln in rs])
+        idx, first = np.unique(idx, return_index=True)  # sorted indices, first reference of each
+        addrs, lens = addrs[first], lens[first]
+        cuts = np.flatnonzero(np.diff(idx) != 1) + 1
+        plan[hx] = [(int(i[0]), a, ln) for i, a, ln in
+                    zip(np.split(idx, cuts), np.split(addrs, cuts), np.split(lens, cuts))]
+    return plan
+
+
 def plan_resident_runs(files) -> dict:
     """Where every xorb chunk of a set of decoded files sits in memory.
 
@@ -171,17 +189,7 @@ def plan_resident_runs(files) -> dict:
             cur += k
         if cur != len(lens):
             raise ValueError(f"file {fi}: terms cover {cur} chunks, chunk_lens has {len(lens)}")
-    plan = {}
-    for hx, rs in refs.items():
-        idx = np.concatenate([np.arange(c0, c0 + len(a), dtype=np.int64) for c0, a, _ in rs])
-        addrs = np.concatenate([a for _, a, _ in rs])
-        lens = np.concatenate([ln for _, _, ln in rs])
-        idx, first = np.unique(idx, return_index=True)  # sorted indices, first reference of each
-        addrs, lens = addrs[first], lens[first]
-        cuts = np.flatnonzero(np.diff(idx) != 1) + 1
-        plan[hx] = [(int(i[0]), a, ln) for i, a, ln in
-                    zip(np.split(idx, cuts), np.split(addrs, cuts), np.split(lens, cuts))]
-    return plan
+    return merge_chunk_refs(refs)
 
 
 _active: list = []  # ResidentSeedServers started by pull(..., seed=...)
