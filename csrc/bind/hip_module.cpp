@@ -292,6 +292,17 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("scratch_bytes"), py::arg("stream"),
      "K12: recs is a device array of ZgReuse records (src address, dst offset, len, table row), pre-validated by "
      "the caller (zest_amd.ops.reuse_chunks)");
+  m.def("dedup_slots", [](uint64_t rows) { return zg_dedup_slots(rows); });
+  m.def("dedup_table_bytes", [](uint64_t rows) { return zg_dedup_table_bytes(rows); });
+  m.def("dedup_chunks", [](uintptr_t index, uint32_t m_rows, uintptr_t fresh, uint32_t n, uintptr_t table,
+                           size_t table_bytes, uintptr_t first, uintptr_t st) {
+    check(zg_dedup_chunks(P<const uint8_t>(index), m_rows, P<const uint8_t>(fresh), n, P<uint32_t>(table), table_bytes,
+                          P<int64_t>(first), S(st)),
+          "zg_dedup_chunks");
+  }, py::arg("index"), py::arg("m"), py::arg("fresh"), py::arg("n"), py::arg("table"), py::arg("table_bytes"),
+     py::arg("first"), py::arg("stream"),
+     "K13: first[j] = smallest row of (index rows, fresh rows) equal to fresh row j; table is scratch of "
+     "dedup_table_bytes(m + n) bytes; pre-validated by the caller (zest_amd.ops.dedup_chunks)");
   m.attr("SLICE_ROWS") = int(ZG_SLICE_ROWS);
   m.def("slice_gather", [](uintptr_t src, uintptr_t table, uint32_t n, uint64_t dst_total, uintptr_t dst,
                            uintptr_t st) {

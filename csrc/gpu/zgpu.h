@@ -243,6 +243,21 @@ typedef struct ZgReuse {
 hipError_t zg_reuse_chunks(const ZgReuse* recs, int n, uint8_t* dst, uint8_t* hashes, uint64_t* sizes,
                            uint8_t* scratch, size_t scratch_bytes, hipStream_t stream);
 
+// K13 (dedup.hip): chunk dedup, a hash join over 32-byte keys.  Rows 0 .. m are `index`, rows
+// m .. m + n are `fresh` (two pointers: a persistent index is never concatenated); both are
+// contiguous rows of 32 bytes, 16-byte aligned.  first[j] (j < n) = the smallest row r' <= m + j whose
+// 32 bytes equal fresh row j's: below m an index row, m + j when fresh row j is the first of its
+// kind.  A pure function of the keys.  table: caller-owned scratch of zg_dedup_table_bytes(m + n)
+// bytes, 16-byte aligned, overwritten by every call: open addressing with linear probing over
+// uint32 row ids in zg_dedup_slots(m + n) slots (the next power of two >= 2 * rows, at least 64);
+// a row's home slot is (little-endian u64 of key bytes 0 .. 8) & (slots - 1).  Size and slot
+// function are part of the contract.  m + n < 2^31; n == 0 launches nothing.  Three launches on
+// `stream` (fill, build, probe).
+uint64_t zg_dedup_slots(uint64_t rows);
+size_t zg_dedup_table_bytes(uint64_t rows);
+hipError_t zg_dedup_chunks(const uint8_t* index, uint32_t m, const uint8_t* fresh, uint32_t n, uint32_t* table,
+                           size_t table_bytes, int64_t* first, hipStream_t stream);
+
 int zg_device_count(void);
 // K6: out[i] (20 B) = SHA1("zest-xet-v1:" || hashes[i] (32 B)); out must be 4-byte aligned.
 hipError_t zg_sha1_info_hash(const uint8_t* hashes, int n, uint8_t* out, hipStream_t stream);

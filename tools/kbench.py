@@ -64,6 +64,58 @@ def main():
         ms = timed(lambda: ops.fill_synthetic(arena, 1, 0, 0), a.iters)
         emit(kernel="fill_synthetic_random", bytes=n, ms=ms, gbps=n / ms / 1e6)
 
+    if want("dedup_chunks"):
+        # K13 at the scale of a 70B model: 2.2 M index rows, 2.2 M fresh rows of which half are index
+        # rows and 1 % repeat an earlier fresh row.  Beside it, in the same run, the host alternative:
+        # the fresh hashes copied to the host and joined there with NumPy on a 32-byte void view
+        # (the index's host copy is taken as given).
+        m_rows = n_rows = 2_200_000
+        g = torch.Generator(device=dev).manual_seed(13)
+        index_h = torch.randint(0, 256, (m_rows, 32), dtype=torch.uint8, device=dev, generator=g)
+        fresh_h = torch.randint(0, 256, (n_rows, 32), dtype=torch.uint8, device=dev, generator=g)
+        hit = torch.randperm(n_rows, device=dev, generator=g)[: n_rows // 2]
+        fresh_h[hit] = index_h[torch.randint(0, m_rows, (len(hit),), device=dev, generator=g)]
+        rep = torch.randint(n_rows // 100, n_rows, (n_rows // 100,), device=dev, generator=g)
+        fresh_h[rep] = fresh_h[torch.randint(0, n_rows // 100, (len(rep),), device=dev, generator=g)]
+        tb = H.dedup_table_bytes(m_rows + n_rows)
+        table = torch.empty(tb, dtype=torch.uint8, device=dev)
+        first = torch.empty(n_rows, dtype=torch.int64, device=dev)
+        ms = timed(lambda: H.dedup_chunks(index_h.data_ptr(), m_rows, fresh_h.data_ptr(), n_rows, table.data_ptr(), tb,
+                                          first.data_ptr(), st), a.iters)
+        emit(kernel="dedup_chunks[3 launches]", index_rows=m_rows, fresh_rows=n_rows, table_bytes=tb, ms=ms,
+             mrows_per_s=(m_rows + n_rows) / ms / 1e3, gbps=32 * (m_rows + n_rows) / ms / 1e6)
+
+        def wall(fn, iters):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                r = fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / iters * 1e3, r
+
+        ms_ops, got = wall(lambda: ops.dedup_chunks(index_h, fresh_h), a.iters)
+        emit(kernel="ops.dedup_chunks[wall, with table allocation]", ms=ms_ops)
+        assert torch.equal(got, first)
+        index_host = np.ascontiguousarray(index_h.cpu().numpy()).view("V32").reshape(-1)
+        ms_d2h, fresh_host = wall(lambda: fresh_h.cpu(), a.iters)
+
+        def host_join():
+            keys = np.concatenate([index_host, fresh_host.numpy().view("V32").reshape(-1)])
+            _, where, inv = np.unique(keys, return_index=True, return_inverse=True)  # where: first row of each key
+            return where[inv.reshape(-1)][m_rows:]
+
+        t0 = time.perf_counter()
+        host_first = host_join()
+        ms_join = (time.perf_counter() - t0) * 1e3
+        emit(kernel="host_join[d2h of fresh hashes + numpy unique on V32]", d2h_ms=ms_d2h, join_ms=ms_join,
+             ms=ms_d2h + ms_join)
+        assert np.array_equal(host_first, first.cpu().numpy()), "kernel and host join disagree"
+        own = m_rows + np.arange(n_rows)
+        emit(kernel="dedup_chunks[result]", matched=int((host_first < m_rows).sum()),
+             duplicates=int(((host_first >= m_rows) & (host_first != own)).sum()), new=int((host_first == own).sum()))
+        del index_h, fresh_h, table, first, got
+
     # fixed 64 KiB chunks over the arena
     csize = 65536
     nck = n // csize

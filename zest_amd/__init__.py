@@ -92,7 +92,8 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       bounds device memory, not network bytes.  Files in which the rank keeps nothing (per
       model.safetensors.index.json) are not fetched.  `stats["shard"]` receives file_bytes, kept_bytes,
       skipped_files, groups, scratch_bytes and gather_s.
-    * base=w0 (the Weights an earlier direct pull returned, its `.resident` set, or a list of those),
+    * base=w0 (the Weights an earlier direct pull returned, its `.resident` set, what
+      `zest_amd.publish` returned, or a list of those),
       device="cuda:N" / "cpu" direct pulls: a delta pull.  Reconstruction terms of the new revision
       whose chunks are all resident in the base's memory on the same device are copied from there and
       re-hashed on the way (ops.reuse_chunks, kernel K12) instead of fetched; the rest takes the usual
@@ -190,6 +191,23 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
 
     res = _client.pull_detailed(repo, revision, **kw)
     return load_snapshot(res.snapshot_dir, device or "cuda:0", res.xet_hashes() if verify else None)
+
+
+def publish(files, **kw):
+    """Publish files resident in GPU (or host) memory as a new, deduplicated Xet revision; see
+    zest_amd.publish.publish.  (Once that module is imported `zest_amd.publish` names the module,
+    which is callable with the same signature.)"""
+    from .publish import publish as _publish
+
+    return _publish(files, **kw)
+
+
+def __getattr__(name: str):
+    if name == "ChunkIndex":  # lazy: importing the package does not import torch
+        from .publish import ChunkIndex
+
+        return ChunkIndex
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def from_pretrained(repo: str, revision: str = "main", **kw):

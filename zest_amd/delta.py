@@ -107,15 +107,18 @@ class ResidentSet:
 
 
 def as_resident_set(base, device) -> ResidentSet:
-    """The `base=` keyword as one ResidentSet on `device`: a Weights, a ResidentSet or a list of
-    either.  Raises ValueError for anything else and for a base on another device."""
+    """The `base=` keyword as one ResidentSet on `device`: a Weights, a ResidentSet, what
+    `zest_amd.publish` returned (a Published) or a list of those.  Raises ValueError for anything
+    else and for a base on another device."""
     dev = _norm_device(device)
     items = list(base) if isinstance(base, (list, tuple)) else [base]
     if not items:
         raise ValueError("base= is empty: pass the Weights of an earlier pull (or leave base= out)")
+    from .publish import Published
+
     out = None
     for b in items:
-        rs = b.resident if isinstance(b, zdev.Weights) else b
+        rs = b.resident if isinstance(b, (zdev.Weights, Published)) else b
         if not isinstance(rs, ResidentSet):
             what = "Weights of a sharded or snapshot pull" if isinstance(b, zdev.Weights) else type(b).__name__
             raise ValueError(f"base= takes the Weights returned by an unsharded direct pull (device='cuda:N' or "

@@ -42,16 +42,22 @@ class Weights(dict):
     tensors are views of.  `pull(repo, new_revision, device=..., base=weights)` copies the chunks the
     new revision shares with them out of this memory instead of fetching them.  The set is built on
     first use from what the pull already had (file buffers, chunk sizes, reconstruction terms): no
-    request, no device memory.  It keeps the file buffers alive as long as it is referenced."""
+    request, no device memory.  It keeps the file buffers alive as long as it is referenced.  The
+    files' paths and Xet hashes are remembered beside the buffers: `zest_amd.publish(weights)`
+    publishes the buffers under those paths, `ChunkIndex.from_weights` checks them against the hashes."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self._files = []  # (buffer, chunk_lens, term_keys) per Xet file
+        self._meta = []   # (path, xet_hash) per Xet file, parallel to _files (zest_amd.publish)
         self._device = None
         self._resident = None
 
-    def _set_files(self, files, device) -> None:
+    def _set_files(self, files, device, meta=None) -> None:
         self._files, self._device, self._resident = list(files), torch.device(device), None
+        self._meta = list(meta) if meta is not None else []
+        if self._meta and len(self._meta) != len(self._files):
+            raise ValueError("meta must name every file")
 
     @property
     def resident(self):

@@ -125,7 +125,7 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
         _add_views(out, buf, f["path"])
         if save_snapshot:
             _save(repo, commit or revision, f["path"], buf)
-    out._set_files(resident, dev)
+    out._set_files(resident, dev, meta=[(f["path"], f["xet_hash"]) for f in xet])
     if plain or save_snapshot:
         inc = [f["path"] for f in plain] + ([f["path"] for f in files if not f["path"].endswith(".safetensors")]
                                            if save_snapshot else [])

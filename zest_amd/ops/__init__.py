@@ -7,7 +7,7 @@ CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/C
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
 K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers,
-K12 reuse_chunks.
+K12 reuse_chunks, K13 dedup_chunks.
 """
 from __future__ import annotations
 
@@ -911,6 +911,84 @@ def reuse_chunks(src_addrs, lens, dst: torch.Tensor, dst_offs, hashes: torch.Ten
     for a, b, _ in parts:  # one stream: the launches run in order and share the scratch
         H.reuse_chunks(tab.data_ptr() + a * REUSE_DTYPE.itemsize, b - a, dst.data_ptr(), hashes.data_ptr(), sz,
                        scratch.data_ptr(), sb, st)
+
+
+# ----------------------------------------------------------------------------------------------
+# K13: chunk dedup, a hash join of fresh chunk hashes against an index of known ones
+# ----------------------------------------------------------------------------------------------
+MAX_DEDUP_ROWS = 1 << 31
+
+
+def dedup_slots(rows: int) -> int:
+    """Slots of K13's table for `rows` rows (index + fresh): the next power of two >= 2 * rows, at
+    least 64.  A row's home slot is (little-endian u64 of its hash bytes 0..8) & (slots - 1).  Part
+    of the kernel's contract (csrc/gpu/zgpu.h, zg_dedup_slots computes the same number)."""
+    rows = int(rows)
+    if rows < 0:
+        raise ValueError("dedup_slots: rows must not be negative")
+    return max(64, 1 << (2 * rows - 1).bit_length()) if rows else 64
+
+
+def _check_hashes(t, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError(f"dedup_chunks: {name} must be a uint8 tensor, got "
+                         f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dim() != 2 or t.shape[1] != 32:
+        raise ValueError(f"dedup_chunks: {name} must have shape [k, 32] (one 32-byte hash per row), got "
+                         f"{list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"dedup_chunks: {name} must be contiguous (rows of 32 bytes end to end); call .contiguous()")
+
+
+def dedup_chunks(index_hashes: torch.Tensor, new_hashes: torch.Tensor, stream=None) -> torch.Tensor:
+    """For every fresh chunk hash, the first row that holds the same 32 bytes: K13, csrc/gpu/dedup.hip.
+
+    index_hashes: uint8 [m, 32], what is already known (m may be 0); new_hashes: uint8 [n, 32].  Rows
+    are numbered index first, then fresh.  Returns int64 [n] on the inputs' device: a value < m is an
+    index row; the value m + j is fresh row j with j <= i, and j == i means row i is the first of its
+    kind.  Among equal rows the smallest wins, so an index row beats a fresh one and the first index
+    row beats a later duplicate; the result is a pure function of the hashes.  Refused on the host
+    (ValueError naming what is wrong): inputs that are not contiguous uint8 [k, 32], inputs on different
+    devices, m + n >= 2**31.  n == 0 returns an empty tensor without a launch.  GPU tensors: three
+    asynchronous launches on `stream` (default: the current stream), the table allocated and freed in
+    that stream's order; CPU tensors: a dict over the rows' bytes with the same rule."""
+    _check_hashes(index_hashes, "index_hashes")
+    _check_hashes(new_hashes, "new_hashes")
+    if index_hashes.device != new_hashes.device:
+        raise ValueError(f"dedup_chunks: index_hashes is on {index_hashes.device}, new_hashes on {new_hashes.device}: "
+                         "move the index to the device of the hashes it is joined with")
+    m, n = index_hashes.shape[0], new_hashes.shape[0]
+    if m + n >= MAX_DEDUP_ROWS:
+        raise ValueError(f"dedup_chunks: {m} + {n} rows, the table's row ids hold fewer than 2**31")
+    dev = new_hashes.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    if dev.type != "cuda":
+        seen: dict[bytes, int] = {}
+        for r, row in enumerate(index_hashes.numpy()):
+            seen.setdefault(row.tobytes(), r)
+        out = np.empty(n, dtype=np.int64)
+        for j, row in enumerate(new_hashes.numpy()):
+            out[j] = seen.setdefault(row.tobytes(), m + j)
+        return torch.from_numpy(out)
+    H = hip()
+    tb = H.dedup_table_bytes(m + n)
+    assert tb == 4 * dedup_slots(m + n), "K13 table size drift"
+
+    def alloc():
+        # rows are 32 bytes, so only a view that starts off a 16-byte boundary needs a copy
+        keys = [t.clone() if t.shape[0] and t.data_ptr() % 16 else t for t in (index_hashes, new_hashes)]
+        return keys, torch.empty(tb, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+
+    if stream is None:
+        st = _stream(dev)
+        (ix, fr), table, first = alloc()
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # allocations, copies and frees are ordered on the launch's stream
+            (ix, fr), table, first = alloc()
+    H.dedup_chunks(ix.data_ptr() if m else 0, m, fr.data_ptr(), n, table.data_ptr(), tb, first.data_ptr(), st)
+    return first
 
 
 # ----------------------------------------------------------------------------------------------

@@ -1,0 +1,406 @@
+"""Publish weights that are resident in memory as a new, deduplicated Xet revision.
+
+    w0 = zest_amd.pull("org/model", "step-100", device="cuda:0")
+    index = zest_amd.ChunkIndex.from_weights(w0)      # before the tensors change
+    ...                                               # a training step updates w0's tensors in place
+    pub = zest_amd.publish(w0, index=index, seed=True)
+    pub.manifest                                      # files, reconstruction terms, new xorbs: JSON-able
+    ...
+    pub2 = zest_amd.publish(w0, index=pub.index)      # step -> step: the index comes from the last call
+
+`publish` is the producing side of the delta pull (zest_amd.delta).  It chunks every file where it
+lies (GearHash candidates K5 + the Xet min/max rule), hashes the chunks (K1), finds every chunk the
+index already knows or that occurred earlier in the same call (`ops.dedup_chunks`, kernel K13: a
+hash join on the device over the 32-byte chunk hashes), packs only the remaining, new chunks into
+new xorbs (`_core.plan_xorbs`, xorb hashes by K2) and writes every file's reconstruction as terms
+into old and new xorbs (file hashes by K2).  No byte is copied: the returned `.resident` set maps
+every xorb chunk the revision references, new or old, to the address in the file buffers where its
+bytes lie, and `seed=True` serves them from there as stored (scheme 0) chunks through the resident
+seeder (`seed.ResidentSeedServer.from_plan`, K9).  A peer pulls the revision with
+`pull(repo, rev, base=its old weights, peers=[publisher])` and fetches only the new chunks; a peer
+without the old revision gets everything from the publisher.
+
+Limits: new chunks are not compressed (resident serving is scheme 0); one device per call; the
+manifest is handed to pullers by whoever runs the hub (`zest_amd.testing.FakeHub.add_manifest`):
+uploading xorbs and shards to a real Hub CAS is not implemented; there is no CLI form, and an index
+lives in its process.
+"""
+from __future__ import annotations
+
+import contextlib
+import json
+import struct
+import sys
+import time
+import types
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _core, ops
+from . import device as zdev
+from .delta import ResidentSet, _norm_device
+from .seed import plan_resident_runs
+
+MAX_XORB_CHUNKS = 8192
+HASH_LAUNCH_BYTES = 1 << 30  # chunk bytes per K1 launch, as ops.reuse_chunks: bounds the hash scratch
+
+
+def _hash_chunks(buf: torch.Tensor, lens: np.ndarray) -> torch.Tensor:
+    """Xet chunk hashes of consecutive chunks of `buf` (uint8 [n, 32] on its device), in launches of
+    at most HASH_LAUNCH_BYTES."""
+    lens = np.asarray(lens, dtype=np.uint32)
+    cum = np.cumsum(lens, dtype=np.uint64)
+    offs = cum - lens
+    cuts = [0] + (np.flatnonzero(np.diff(cum // np.uint64(HASH_LAUNCH_BYTES))) + 1).tolist() + [len(lens)]
+    parts = [ops.hash_ranges(buf, offs[a:b], lens[a:b]) for a, b in zip(cuts, cuts[1:]) if b > a]
+    return torch.cat(parts) if len(parts) != 1 else parts[0]
+
+
+class ChunkIndex:
+    """What the swarm already has, chunk by chunk: `hashes` (uint8 [M, 32], on the device the join
+    runs on), the parallel host arrays `xorb_id` / `chunk` (row r is chunk `chunk[r]` of xorb
+    `xorbs[xorb_id[r]]`) and `xorbs`, the xorb hashes as Xet hex.  Rows need not be unique: the first
+    row of a hash is the one `publish` refers to.  `a | b` unites two indexes, a's rows first."""
+
+    def __init__(self, hashes: torch.Tensor, xorb_id, chunk, xorbs):
+        if hashes.dtype != torch.uint8 or hashes.dim() != 2 or hashes.shape[1] != 32:
+            raise ValueError("ChunkIndex: hashes must be a uint8 [M, 32] tensor")
+        self.hashes = hashes.contiguous()
+        self.xorb_id = np.ascontiguousarray(xorb_id, dtype=np.int64)
+        self.chunk = np.ascontiguousarray(chunk, dtype=np.int64)
+        self.xorbs = list(xorbs)
+        m = self.hashes.shape[0]
+        if self.xorb_id.shape != (m,) or self.chunk.shape != (m,):
+            raise ValueError("ChunkIndex: xorb_id and chunk must have one entry per hash")
+        if m and (self.xorb_id.min() < 0 or self.xorb_id.max() >= len(self.xorbs)):
+            raise ValueError("ChunkIndex: xorb_id outside the xorb list")
+
+    @classmethod
+    def empty(cls, device) -> "ChunkIndex":
+        return cls(torch.empty((0, 32), dtype=torch.uint8, device=device), [], [], [])
+
+    @property
+    def device(self) -> torch.device:
+        return _norm_device(self.hashes.device)
+
+    def __len__(self) -> int:
+        return self.hashes.shape[0]
+
+    def to(self, device) -> "ChunkIndex":
+        return ChunkIndex(self.hashes.to(device), self.xorb_id, self.chunk, self.xorbs)
+
+    def __or__(self, other: "ChunkIndex") -> "ChunkIndex":
+        if not isinstance(other, ChunkIndex):
+            return NotImplemented
+        if other.device != self.device:
+            raise ValueError(f"chunk indexes on different devices ({self.device}, {other.device}) do not merge: "
+                             "move one with .to(device)")
+        pos = {hx: i for i, hx in enumerate(self.xorbs)}
+        xorbs = list(self.xorbs)
+        remap = np.empty(len(other.xorbs), dtype=np.int64)
+        for i, hx in enumerate(other.xorbs):
+            if hx not in pos:
+                pos[hx] = len(xorbs)
+                xorbs.append(hx)
+            remap[i] = pos[hx]
+        return ChunkIndex(torch.cat([self.hashes, other.hashes]),
+                          np.concatenate([self.xorb_id, remap[other.xorb_id] if len(other) else other.xorb_id]),
+                          np.concatenate([self.chunk, other.chunk]), xorbs)
+
+    @classmethod
+    def from_weights(cls, w) -> "ChunkIndex":
+        """The index of a direct pull's `Weights`: every chunk of its Xet files, re-hashed from the
+        file buffers as they are now, located through the files' reconstruction terms.  Every file's
+        Merkle file hash is then compared with the Xet hash the pull verified: an index of bytes that
+        were modified since would point peers at xorb chunks that hold other bytes, so a file that no
+        longer matches raises VerifyError.  Take the index before modifying the tensors."""
+        if not isinstance(w, zdev.Weights) or w._device is None:
+            raise ValueError("ChunkIndex.from_weights takes the Weights an unsharded direct pull returned "
+                             "(device='cuda:N' or 'cpu')")
+        if len(w._meta) != len(w._files):
+            raise ValueError("these Weights do not record their files' paths and Xet hashes: pull them again")
+        dev = w._device
+        if not w._files:
+            return cls.empty(dev)
+        pos: dict[str, int] = {}
+        xorbs, hashes, sizes, xid, cidx, jobs, leaf0 = [], [], [], [], [], [], 0
+        for (path, _), (buf, chunk_lens, keys) in zip(w._meta, w._files):
+            lens = (np.frombuffer(chunk_lens, dtype="<u4") if isinstance(chunk_lens, (bytes, bytearray, memoryview))
+                    else np.asarray(chunk_lens)).astype(np.uint32)
+            cur = 0
+            for hx, c0, c1 in keys:
+                if hx not in pos:
+                    pos[hx] = len(xorbs)
+                    xorbs.append(hx)
+                k = int(c1) - int(c0)
+                xid.append(np.full(k, pos[hx], dtype=np.int64))
+                cidx.append(np.arange(int(c0), int(c1), dtype=np.int64))
+                cur += k
+            if cur != len(lens) or int(lens.sum(dtype=np.uint64)) != buf.numel():
+                raise ValueError(f"{path}: terms cover {cur} chunks, the file has {len(lens)}")
+            hashes.append(_hash_chunks(buf, lens))
+            sizes.append(lens.astype(np.int64))
+            jobs.append((leaf0, len(lens)))
+            leaf0 += len(lens)
+        hashes = torch.cat(hashes)
+        sizes_d = torch.from_numpy(np.concatenate(sizes)).to(dev)
+        roots = ops.merkle_roots(hashes, sizes_d, jobs, file_hash=True).cpu().numpy()
+        for (path, want), root in zip(w._meta, roots):
+            got = _core.xet_hex(root.tobytes())
+            if got != want:
+                raise zdev.VerifyError(f"{path}: the bytes in memory hash to {got}, the pull verified {want}: the "
+                                       "tensors were modified since; take the index (ChunkIndex.from_weights) "
+                                       "before modifying the tensors")
+        return cls(hashes, np.concatenate(xid), np.concatenate(cidx), xorbs)
+
+
+@dataclass
+class Published:
+    """What `publish` returns.  manifest: the revision's metadata, JSON-able; index: the ChunkIndex
+    of every chunk of this revision (its hashes come from this call, so the next publish can take it
+    although the tensors keep changing); resident: a `delta.ResidentSet` over the file buffers that
+    covers every xorb chunk the revision references; stats: counters and seconds per phase; server:
+    the resident seed server when `seed=` asked for one."""
+    manifest: dict
+    index: ChunkIndex
+    resident: ResidentSet
+    stats: dict = field(default_factory=dict)
+    server: object = None
+
+    @property
+    def port(self):
+        return self.server.port if self.server is not None else None
+
+    def json(self) -> str:
+        return json.dumps(self.manifest, separators=(",", ":"))
+
+
+def _file_set(files):
+    """[(path, buffer)] sorted by path and the device they are on."""
+    if isinstance(files, zdev.Weights):
+        if files._device is None or not files._files:
+            raise ValueError("publish: these Weights hold no Xet file buffers (an empty file set): publish the "
+                             "Weights of an unsharded direct pull, or a {path: uint8 tensor} dict")
+        if len(files._meta) != len(files._files):
+            raise ValueError("publish: these Weights do not record their files' paths: pull them again")
+        items = [(path, buf) for (path, _), (buf, _, _) in zip(files._meta, files._files)]
+    elif isinstance(files, dict):
+        if not files:
+            raise ValueError("publish: the file set is empty: pass {path: uint8 tensor holding the whole file} or "
+                             "the Weights of a direct pull")
+        items = list(files.items())
+    else:
+        raise ValueError(f"publish takes {{path: uint8 tensor}} or the Weights of a direct pull, got "
+                         f"{type(files).__name__}")
+    for path, buf in items:
+        if not isinstance(path, str) or not isinstance(buf, torch.Tensor):
+            raise ValueError("publish: files must map path strings to tensors")
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+            raise ValueError(f"publish: {path} must be a contiguous 1-D uint8 tensor holding the whole file "
+                             "(pack_safetensors builds one from loose tensors)")
+        if buf.numel() == 0:
+            raise ValueError(f"publish: {path} is empty: an empty file has no chunks to publish; leave it out")
+    devs = {_norm_device(b.device) for _, b in items}
+    if len(devs) > 1:
+        raise ValueError(f"publish: files on more than one device ({', '.join(sorted(map(str, devs)))}): one call "
+                         "publishes from one device; move the files to one device or publish per device")
+    return sorted(items, key=lambda it: it[0]), devs.pop()
+
+
+def publish(files, *, index: ChunkIndex | None = None, seed=False, max_xorb_bytes: int = 64 << 20,
+            stats: dict | None = None) -> Published:
+    """Publish files that lie in memory as a new Xet revision, deduplicated against `index`.
+
+    files: `{path: contiguous uint8 tensor holding the whole file}`, all on one device, or a
+    `Weights`, whose file buffers and recorded paths are published in their current state (tensors
+    updated in place are the normal case; only its Xet-backed files have buffers, small plain files
+    of the repository are the hub's to carry over).  index: the `ChunkIndex` of what the swarm already has
+    (None: nothing).  Files are processed in sorted path order, so the result is deterministic.  A
+    chunk the index knows becomes a reference to its old xorb; a chunk repeated across or within the
+    files is stored once; the rest is packed into new xorbs of at most `max_xorb_bytes` serialized
+    bytes and 8192 chunks, uncompressed.  Nothing is copied.
+
+    seed=True (or a port): `.resident` is served to BEP XET peers by a resident seed server,
+    registered like a pull's (`zest_amd.seed.active()`, `stop_all()`).  The seeded buffers must stay
+    read-only until the server stops, as for every resident seeder: bytes changed in place no longer
+    match their chunk hashes and receivers drop them.  A training loop publishes clones, or stops
+    the server before the next step.
+
+    stats (and `.stats`): files, bytes, chunks, new / matched (found in the index) / duplicate
+    (repeated in this call) chunks and bytes, new_xorbs, and seconds per phase (cdc, select, hash,
+    dedup, plan, merkle)."""
+    from . import seed as zseed
+
+    items, dev = _file_set(files)
+    cuda = dev.type == "cuda"
+    port = zseed.seed_port(seed)
+    if port is not None and not cuda:
+        raise ValueError(f"publish: seed= serves from GPU memory, these files are on {dev}: publish from "
+                         "device='cuda:N' tensors to seed, or hand the bytes to the hub yourself")
+    if index is not None:
+        if not isinstance(index, ChunkIndex):
+            raise ValueError("publish: index= takes a ChunkIndex (ChunkIndex.from_weights, or an earlier "
+                             "Published.index)")
+        if index.device != dev:
+            raise ValueError(f"publish: the index is on {index.device} but the files are on {dev}: the join runs on "
+                             "one device; move the index with index.to(device)")
+    if index is None:
+        index = ChunkIndex.empty(dev)
+    sec = dict.fromkeys(("cdc", "select", "hash", "dedup", "plan", "merkle"), 0.0)
+
+    def lap(key: str, t0: float) -> float:
+        if cuda:
+            torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        sec[key] += t1 - t0
+        return t1
+
+    with torch.cuda.device(dev) if cuda else contextlib.nullcontext():
+        # 1 + 2: chunk boundaries and chunk hashes, file by file
+        lens_f, hashes_f = [], []
+        for path, buf in items:
+            n = buf.numel()
+            t = time.perf_counter()
+            if cuda:
+                src = ops._as_padded_u8(buf)  # a pull's buffers are padded; others are copied once, for both kernels
+                cands = ops.cdc_candidates(src)
+                t = lap("cdc", t)
+                ends = ops.select_chunks(cands, n)
+            else:
+                src = buf
+                ends = np.asarray(_core.chunk_ends(buf.numpy()), dtype=np.uint64)  # the host chunker: scan + rule
+                t = lap("cdc", t)
+            lens = np.diff(np.concatenate([[0], ends]).astype(np.uint64)).astype(np.uint32)
+            t = lap("select", t)
+            hashes_f.append(_hash_chunks(src, lens))
+            lap("hash", t)
+            lens_f.append(lens)
+            del src
+        counts = [len(ln) for ln in lens_f]
+        leaf0 = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        lens = np.concatenate(lens_f)
+        hashes = torch.cat(hashes_f) if len(hashes_f) != 1 else hashes_f[0]
+        N, m = len(lens), len(index)
+
+        # 3: the join over (index, every file's chunks)
+        t = time.perf_counter()
+        ref = ops.dedup_chunks(index.hashes, hashes).cpu().numpy()
+        t = lap("dedup", t)
+
+        # 4: new rows, in order, into xorbs
+        own = m + np.arange(N, dtype=np.int64)
+        is_new, is_old = ref == own, ref < m
+        new_rows = np.flatnonzero(is_new)
+        xorb_of = np.asarray(_core.plan_xorbs(lens[new_rows].astype(np.uint64) + np.uint64(8), int(max_xorb_bytes),
+                                              MAX_XORB_CHUNKS), dtype=np.int64)
+        x_first = np.flatnonzero(np.concatenate([[True], xorb_of[1:] != xorb_of[:-1]])) if len(xorb_of) else \
+            np.zeros(0, np.int64)
+        x_count = np.diff(np.concatenate([x_first, [len(xorb_of)]]))
+        t = lap("plan", t)
+
+        # 5 + 6: xorb hashes over the compacted new rows, file hashes over each file's leaves
+        sizes_d = torch.from_numpy(lens.astype(np.int64)).to(dev)
+        if len(new_rows):
+            sel = torch.from_numpy(new_rows).to(dev)
+            xroots = ops.merkle_roots(hashes.index_select(0, sel), sizes_d.index_select(0, sel),
+                                      [(int(a), int(k)) for a, k in zip(x_first, x_count)], file_hash=False)
+            new_hex = [_core.xet_hex(r.tobytes()) for r in xroots.cpu().numpy()]
+        else:
+            new_hex = []
+        froots = ops.merkle_roots(hashes, sizes_d, [(int(leaf0[i]), counts[i]) for i in range(len(items))],
+                                  file_hash=True).cpu().numpy()
+        t = lap("merkle", t)
+
+    # where every chunk of the revision lives: (xorb, chunk index) per row
+    xorbs = list(index.xorbs) + new_hex
+    loc_x, loc_c = np.empty(N, dtype=np.int64), np.empty(N, dtype=np.int64)
+    loc_x[new_rows] = len(index.xorbs) + xorb_of
+    loc_c[new_rows] = np.arange(len(new_rows), dtype=np.int64) - np.repeat(x_first, x_count)
+    old_rows = np.flatnonzero(is_old)
+    loc_x[old_rows], loc_c[old_rows] = index.xorb_id[ref[old_rows]], index.chunk[ref[old_rows]]
+    dup_rows = np.flatnonzero(~is_new & ~is_old)  # an earlier fresh row, which is a new one
+    loc_x[dup_rows], loc_c[dup_rows] = loc_x[ref[dup_rows] - m], loc_c[ref[dup_rows] - m]
+
+    # 7: per file, terms as maximal runs of chunks that are consecutive in one xorb
+    man_files, res_files = [], []
+    for i, (path, buf) in enumerate(items):
+        a, b = int(leaf0[i]), int(leaf0[i + 1])
+        x, c, ln = loc_x[a:b], loc_c[a:b], lens[a:b]
+        cuts = np.concatenate([[0], np.flatnonzero((x[1:] != x[:-1]) | (c[1:] != c[:-1] + 1)) + 1, [b - a]])
+        terms = [[xorbs[int(x[s])], int(c[s]), int(c[e - 1]) + 1, int(ln[s:e].sum(dtype=np.uint64))]
+                 for s, e in zip(cuts, cuts[1:])]
+        man_files.append({"path": path, "size": int(buf.numel()), "xet_hash": _core.xet_hex(froots[i].tobytes()),
+                          "terms": terms})
+        res_files.append((buf, ln, [(hx, c0, c1) for hx, c0, c1, _ in terms]))
+    manifest = {"version": 1, "files": man_files,
+                "xorbs": {hx: {"chunk_lens": [int(v) for v in lens[new_rows[a:a + k]]]}
+                          for hx, a, k in zip(new_hex, x_first, x_count)}}
+    sec["plan"] += time.perf_counter() - t  # host work: locations, terms, manifest
+
+    used, inv = np.unique(loc_x, return_inverse=True)  # the next index names only xorbs this revision references
+    out_index = ChunkIndex(hashes, inv.reshape(-1), loc_c, [xorbs[int(u)] for u in used])
+    resident = ResidentSet(plan_resident_runs([(b.data_ptr(), ln, keys) for b, ln, keys in res_files]),
+                           [b for b, _, _ in res_files], dev)
+    nbytes = lambda rows: int(lens[rows].sum(dtype=np.uint64))
+    info = {"files": len(items), "bytes": int(lens.sum(dtype=np.uint64)), "chunks": N,
+            "new_chunks": len(new_rows), "matched_chunks": len(old_rows), "duplicate_chunks": len(dup_rows),
+            "new_bytes": nbytes(new_rows), "matched_bytes": nbytes(old_rows), "duplicate_bytes": nbytes(dup_rows),
+            "new_xorbs": len(new_hex), "seconds": sec}
+    if stats is not None:
+        stats.update(info)
+    pub = Published(manifest, out_index, resident, info)
+    if port is not None:
+        pub.server = zseed.ResidentSeedServer.from_plan(resident.plan, resident.buffers, dev, port)
+        zseed._active.append(pub.server)
+    return pub
+
+
+_ST_NAMES = {v: k for k, v in zdev.ST_DTYPES.items()}
+
+
+def pack_safetensors(tensors: dict, metadata: dict | None = None) -> torch.Tensor:
+    """One safetensors file in memory from loose tensors: a uint8 buffer on the tensors' device
+    holding the header and every tensor's bytes in dict order (plain copies, no kernel; on a GPU the
+    buffer is padded for the kernels that read it).  For callers whose tensors are not views of a
+    pulled file; `publish({path: pack_safetensors(tensors)})`."""
+    if not tensors:
+        raise ValueError("pack_safetensors: no tensors")
+    devs = {_norm_device(t.device) for t in tensors.values()}
+    if len(devs) > 1:
+        raise ValueError("pack_safetensors: tensors on more than one device")
+    dev = devs.pop()
+    head, off = {}, 0
+    if metadata:
+        head["__metadata__"] = {str(k): str(v) for k, v in metadata.items()}
+    for name, t in tensors.items():
+        dt = _ST_NAMES.get(t.dtype)
+        if dt is None:
+            raise ValueError(f"pack_safetensors: {name}: dtype {t.dtype} has no safetensors name")
+        n = t.numel() * t.element_size()
+        head[name] = {"dtype": dt, "shape": list(t.shape), "data_offsets": [off, off + n]}
+        off += n
+    hb = json.dumps(head, separators=(",", ":")).encode()
+    hb += b" " * (-len(hb) % 8)
+    total = 8 + len(hb) + off
+    buf = ops.padded_empty(total, dev) if dev.type == "cuda" else torch.empty(total, dtype=torch.uint8)
+    buf[:8 + len(hb)].copy_(torch.frombuffer(bytearray(struct.pack("<Q", len(hb)) + hb), dtype=torch.uint8))
+    at = 8 + len(hb)
+    for t in tensors.values():
+        n = t.numel() * t.element_size()
+        if n:
+            buf[at:at + n].copy_(t.contiguous().reshape(-1).view(torch.uint8))
+        at += n
+    return buf
+
+
+class _CallableModule(types.ModuleType):
+    """`zest_amd.publish` names this module once it is imported and the function before: calling the
+    module publishes, so `zest_amd.publish(files, ...)` works either way."""
+
+    def __call__(self, *a, **kw):
+        return publish(*a, **kw)
+
+
+sys.modules[__name__].__class__ = _CallableModule

@@ -244,6 +244,98 @@ class FakeHub:
                                 {revision: world.commit, world.commit: world.commit})
         return world.commit
 
+    def add_manifest(self, repo_id: str, manifest: dict, revision: str = "main", extra_files: dict | None = None,
+                     payload: dict | None = None, commit: str | None = None) -> str:
+        """Publish the revision a `zest_amd.publish` manifest describes; returns the commit sha.
+
+        The manifest's new xorbs are registered by their sizes only, as add_world(payload=False) does:
+        listings, reconstructions and hashes are real, xorb GETs answer 404 (counted as `xorb_missing`),
+        so the bytes have to come from peers (the publisher's resident seeder).  A term that names a
+        xorb this hub already knows resolves to it; one that names an unknown xorb the manifest does
+        not describe raises, as does a term outside its xorb or with another unpacked length.
+        payload={path: bytes of the file}: the hub builds the new xorbs' bodies from those bytes
+        (uncompressed) and serves them; a body whose hash differs from the manifest's raises, so this
+        checks the publisher's xorb hashes independently.  extra_files: plain files of the revision."""
+        if manifest.get("version") != 1:
+            raise ValueError(f"add_manifest: manifest version {manifest.get('version')!r}, this hub reads version 1")
+        new = {hx: [int(v) for v in x["chunk_lens"]] for hx, x in manifest.get("xorbs", {}).items()}
+        idx_of = dict(self.xorb_index)
+        for k, hx in enumerate(h for h in new if h not in idx_of):
+            idx_of[hx] = len(self.xorbs) + k
+
+        def ulens(hx):
+            return new[hx] if hx in new and hx not in self.xorb_index else self.xorbs[self.xorb_index[hx]].ulens
+
+        files, chunks = [], {}  # chunks: (new xorb hex, chunk index) -> its bytes, with payload
+        for f in manifest["files"]:
+            data = payload.get(f["path"]) if payload is not None else None
+            if payload is not None and (data is None or len(data) != f["size"]):
+                raise ValueError(f"add_manifest: payload has no {f['size']} bytes for {f['path']}")
+            terms, pos = [], 0
+            for hx, c0, c1, ulen in f["terms"]:
+                if hx not in idx_of:
+                    raise ValueError(f"add_manifest: {f['path']}: term names xorb {hx}, which this hub does not know "
+                                     "and the manifest does not describe")
+                ln = ulens(hx)
+                if not 0 <= c0 < c1 <= len(ln) or sum(ln[c0:c1]) != ulen:
+                    raise ValueError(f"add_manifest: {f['path']}: term [{c0}, {c1}) of {hx} does not match the xorb")
+                if data is not None and hx in new and hx not in self.xorb_index:
+                    at = pos
+                    for c in range(c0, c1):
+                        chunks.setdefault((hx, c), data[at:at + ln[c]])
+                        at += ln[c]
+                terms.append((idx_of[hx], int(c0), int(c1)))
+                pos += ulen
+            if pos != f["size"]:
+                raise ValueError(f"add_manifest: {f['path']}: terms cover {pos} bytes, the file has {f['size']}")
+            files.append((f, terms, data))
+        bodies = {}
+        for hx, ln in new.items():
+            if hx in self.xorb_index or payload is None:
+                continue
+            b = _core.XorbBuilder("none")
+            for c in range(len(ln)):
+                if (hx, c) not in chunks:
+                    raise ValueError(f"add_manifest: no file of the manifest references chunk {c} of new xorb {hx}")
+                b.add_chunk(chunks[(hx, c)])
+            got = _core.xet_hex(b.hash())
+            if got != hx:
+                raise ValueError(f"add_manifest: the bytes of new xorb {hx} hash to {got}")
+            bodies[hx] = b.serialize(True)
+        commit = commit or hashlib.sha1(repr((repo_id, revision, sorted((f["path"], f["xet_hash"])
+                                                                        for f in manifest["files"]))).encode()).hexdigest()
+        out: dict[str, _File] = {}
+        with self.lock:
+            for hx, ln in new.items():
+                if hx in self.xorb_index:
+                    continue
+                self.xorb_index[hx] = len(self.xorbs)
+                assert self.xorb_index[hx] == idx_of[hx]
+                self.xorbs.append(_Xorb(bodies.get(hx), hx, np.cumsum(np.asarray(ln, dtype=np.int64) + 8).tolist(), ln))
+            for f, terms, data in files:
+                if data is not None:
+                    ff = _File(f["path"], bytes(data))
+                else:
+                    ff = _LazyFile(f["path"], b"", size=int(f["size"]))
+                    ff._oid = hashlib.sha1(f["xet_hash"].encode()).hexdigest()
+                    ff._sha256 = hashlib.sha256(f["xet_hash"].encode()).hexdigest()
+                ff.xet_hash, ff.terms = f["xet_hash"], terms
+                self.file_index[ff.xet_hash] = ff
+                out[ff.path] = ff
+            for path, data in (extra_files or {}).items():
+                out[path] = _File(path, bytes(data))
+        for ff in out.values():
+            ff.digests()
+        key = ("model", repo_id)
+        if key in self.repos:
+            repo = self.repos[key]
+            repo.revisions[revision] = commit
+            repo.files, repo.commit = out, commit
+        else:
+            self.repos[key] = _Repo(repo_id, "model", commit, out, {revision: commit, commit: commit})
+        self.repos[key].revisions[commit] = commit
+        return commit
+
     def _ingest(self, f: _File) -> None:
         data = f.data
         ends = _core.chunk_ends(data)
