@@ -292,6 +292,27 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("scratch_bytes"), py::arg("stream"),
      "K12: recs is a device array of ZgReuse records (src address, dst offset, len, table row), pre-validated by "
      "the caller (zest_amd.ops.reuse_chunks)");
+  m.attr("HASH_AT_BYTES") = sizeof(ZgHashAt);
+  m.def("hash_chunks_at", [](uintptr_t recs, int n, uintptr_t hashes, uintptr_t sizes, uintptr_t scratch,
+                             size_t scratch_bytes, uintptr_t st) {
+    check(zg_hash_chunks_at(P<const ZgHashAt>(recs), n, P<uint8_t>(hashes), P<uint64_t>(sizes), P<uint8_t>(scratch),
+                            scratch_bytes, S(st)),
+          "zg_hash_chunks_at");
+  }, py::arg("recs"), py::arg("n"), py::arg("hashes"), py::arg("sizes"), py::arg("scratch"), py::arg("scratch_bytes"),
+     py::arg("stream"),
+     "K12 without the copy: recs is a device array of ZgHashAt records (address, len, table row), pre-validated by "
+     "the caller (zest_amd.ops.hash_chunks_at)");
+  m.attr("SEG_BYTES") = sizeof(ZgSeg);
+  m.def("cdc_candidates_segs", [](uintptr_t segs, uintptr_t win_prefix, uint32_t n_segs, uint64_t n_windows,
+                                  uintptr_t lead, uint64_t mask, uintptr_t out, uintptr_t count, uint64_t cap,
+                                  uintptr_t st) {
+    check(zg_cdc_candidates_segs(P<const ZgSeg>(segs), P<const uint64_t>(win_prefix), n_segs, n_windows,
+                                 P<uint8_t>(lead), mask, P<uint64_t>(out), P<unsigned long long>(count), cap, S(st)),
+          "zg_cdc_candidates_segs");
+  }, py::arg("segs"), py::arg("win_prefix"), py::arg("n_segs"), py::arg("n_windows"), py::arg("lead"),
+     py::arg("mask"), py::arg("out"), py::arg("count"), py::arg("capacity"), py::arg("stream"),
+     "K14: K5 over a device table of ZgSeg segments (address, len, file offset), pre-validated by the caller "
+     "(zest_amd.ops.cdc_candidates_segments)");
   m.def("dedup_slots", [](uint64_t rows) { return zg_dedup_slots(rows); });
   m.def("dedup_table_bytes", [](uint64_t rows) { return zg_dedup_table_bytes(rows); });
   m.def("dedup_chunks", [](uintptr_t index, uint32_t m_rows, uintptr_t fresh, uint32_t n, uintptr_t table,

@@ -78,6 +78,10 @@ struct ReuseIdx {
   const ZgReuse* recs;
   __device__ __forceinline__ uint32_t operator()(int c) const { return recs[c].index; }
 };
+struct AtIdx {
+  const ZgHashAt* recs;
+  __device__ __forceinline__ uint32_t operator()(int c) const { return recs[c].index; }
+};
 
 // Descriptor sources: the bytes + length of message c, or bad (hashed as described per source).
 struct ChunkSrc {  // placed Xet chunks (k_hash_chunks semantics: a bad descriptor hashes as empty)
@@ -188,6 +192,25 @@ struct ReuseSrc {
     p = reinterpret_cast<const uint8_t*>(uintptr_t(r.src));
   }
   __device__ __forceinline__ void report(int) const {}
+};
+
+// zg_hash_chunks_at: ReuseSrc without the copy.  Record c's bytes are hashed where they lie, at an
+// absolute address of any alignment (a chunk of a loose tensor, of a publish call's header tensor or
+// of its seam arena), through hash_leaf_exact like K12's, so a chunk may end at the last byte of its
+// allocation.  Hash and size go to row rec.index; nothing else is stored.
+struct AtSrc {
+  const ZgHashAt* recs;
+  static constexpr bool kBadIsFF = false;
+  static constexpr bool kPlace = false;
+  static constexpr bool kReuse = true;  // records with their own row, exact loads
+  __host__ __device__ AtIdx rows() const { return {recs}; }
+  __device__ __forceinline__ void get(int c, const uint8_t*& p, uint32_t& len, bool& bad) const {
+    const ZgHashAt r = recs[c];
+    len = r.len;
+    bad = len > kMaxChunk;
+    if (bad) len = 0;
+    p = reinterpret_cast<const uint8_t*>(uintptr_t(r.src));
+  }
 };
 
 template <class Src>
@@ -521,6 +544,11 @@ hipError_t zg_hash_ranges_flat(const uint8_t* buf, const uint64_t* offsets, cons
 hipError_t zg_reuse_chunks(const ZgReuse* recs, int n, uint8_t* dst, uint8_t* hashes, uint64_t* sizes,
                            uint8_t* scratch, size_t scratch_bytes, hipStream_t stream) {
   return launch_flat(ReuseSrc{recs, dst}, n, 0, hashes, sizes, scratch, scratch_bytes, stream);
+}
+
+hipError_t zg_hash_chunks_at(const ZgHashAt* recs, int n, uint8_t* hashes, uint64_t* sizes, uint8_t* scratch,
+                             size_t scratch_bytes, hipStream_t stream) {
+  return launch_flat(AtSrc{recs}, n, 0, hashes, sizes, scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// K5 GearHash CDC candidates, K7 xorb packing, and synthetic-content generators (gfx950).
+// K5 GearHash CDC candidates, K14 the same over a segment list, K7 xorb packing, and
+// synthetic-content generators (gfx950).
 //
 // CDC: the Xet gear hash only depends on the last 64 bytes (h = (h << 1) + G[b]), so every
 // position's hash is recomputable from a 63-byte warm-up: each lane scans its own 256-byte
@@ -80,6 +81,112 @@ __global__ void __launch_bounds__(256) k_cdc_candidates(const uint8_t* __restric
         if (gear_zero<kHiOnly>(g, mask)) {
           const unsigned long long k = atomicAdd(count, 1ull);
           if (k < cap) out[k] = v - shift + 1;
+        }
+      }
+    }
+  }
+}
+
+// K14: K5 over a file that is a list of segments (loose tensors, published where they lie).
+//
+// The work item is K5's: a lane owns one 2 KiB window of a segment's aligned address space, clipped
+// to the segment, and steps through it 128 bytes at a time.  The window -> (segment, window in
+// segment) map is implicit: the host uploads the prefix count of windows per segment (a few hundred
+// entries for a 70B model, where a per-window table would be over 1 GB); a wave binary-searches it
+// once, with scalar loads, for its first lane and the lanes walk forward from there (a wave spans
+// at most 64 segments, and almost always one).  Windows 1.. of a segment warm up from the 128 bytes
+// before them, which lie in the same segment (a window starts at a multiple of 2048 of the aligned
+// space, at least 2033 bytes into the segment).  Window 0 starts with the segment: its history is
+// the end of the previous segments, which k_seg_lead gathered into the segment's 64-byte lead-in
+// row; the first segment has none, and h starts from 0 as the scalar scan of the file does.
+__global__ void __launch_bounds__(64) k_seg_lead(const ZgSeg* __restrict__ segs, uint8_t* __restrict__ lead) {
+  const uint32_t s = blockIdx.x, j = threadIdx.x;
+  const uint64_t vstart = segs[s].vstart;
+  const uint64_t L = vstart < 64 ? vstart : 64;  // file bytes before the segment, at most the gear window
+  if (j >= L) return;
+  const uint64_t p = vstart - L + j;  // lies in a segment before s
+  uint32_t lo = 0, hi = s - 1;        // L > 0, so s >= 1
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (segs[mid].vstart <= p) lo = mid;
+    else hi = mid - 1;
+  }
+  lead[64 * uint64_t(s) + j] = reinterpret_cast<const uint8_t*>(uintptr_t(segs[lo].addr))[p - segs[lo].vstart];
+}
+
+template <bool kHiOnly>
+__global__ void __launch_bounds__(256) k_cdc_candidates_segs(const ZgSeg* __restrict__ segs,
+                                                             const uint64_t* __restrict__ wpre, uint32_t nseg,
+                                                             const uint8_t* __restrict__ lead, uint64_t mask,
+                                                             uint64_t* __restrict__ out, unsigned long long* count,
+                                                             uint64_t cap) {
+  __shared__ uint64_t gear[256];
+  gear[threadIdx.x] = kGearDev[threadIdx.x];
+  __syncthreads();
+  const uint64_t W = wpre[nseg];
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t t0 = (uint64_t(blockIdx.x) * 4 + wave) * 64;  // the wave's first window: uniform
+  if (t0 >= W) return;
+  uint32_t lo = 0, hi = nseg - 1;  // the segment of window t0: the last s with wpre[s] <= t0
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (wpre[mid] <= t0) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint64_t t = t0 + (threadIdx.x & 63);
+  if (t >= W) return;
+  uint32_t s = lo;
+  while (t >= wpre[s + 1]) ++s;  // every segment has a window, and t < W = wpre[nseg]
+  const ZgSeg sg = segs[s];
+  const uint64_t win = t - wpre[s];
+  const uint32_t shift = uint32_t(sg.addr & 15);
+  const uint4* base = reinterpret_cast<const uint4*>(uintptr_t(sg.addr - shift));  // position v = index + shift
+  const uint64_t vend = sg.len + shift;
+  const uint64_t vs = win * kSeg;  // < vend by the window count
+  const uint64_t ve = vs + kSeg < vend ? vs + kSeg : vend;
+  uint64_t h = 0;
+  if (win == 0) {  // the history before the segment, oldest byte first
+    const uint32_t L = sg.vstart < 64 ? uint32_t(sg.vstart) : 64u;
+    const uint8_t* lp = lead + 64 * uint64_t(s);
+    for (uint32_t j = 0; j < L; ++j) h = (h << 1) + gear[lp[j]];
+  }
+  // from here on K5's loop; a block [16 m, 16 m + 16) is loaded only when 16 m < vend, and such a
+  // block holds a byte of the segment (m >= 1: byte 16 m >= shift; m = 0: byte shift, as len >= 1)
+  for (uint64_t q = win ? vs - kStep : vs; q < ve; q += kStep) {
+    uint32_t w[kStep / 4];
+#pragma unroll
+    for (int k = 0; k < int(kStep / 16); ++k) {
+      const uint4 x = q + 16 * k < vend ? base[(q >> 4) + k] : make_uint4(0, 0, 0, 0);
+      w[4 * k] = x.x;
+      w[4 * k + 1] = x.y;
+      w[4 * k + 2] = x.z;
+      w[4 * k + 3] = x.w;
+    }
+    const bool warm = q < vs;
+    const uint64_t h0 = h;
+    bool any = false;
+    if (q >= shift && q + kStep <= vend) {
+#pragma unroll
+      for (int j = 0; j < int(kStep); ++j) {
+        h = (h << 1) + gear[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+        any |= gear_zero<kHiOnly>(h, mask);
+      }
+    } else {
+      for (int j = 0; j < int(kStep); ++j) {
+        if (q + j < shift || q + j >= vend) continue;
+        h = (h << 1) + gear[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+        any |= gear_zero<kHiOnly>(h, mask);
+      }
+    }
+    if (any && !warm) {  // rare: replay the step's bytes and emit END offsets in file coordinates
+      uint64_t g = h0;
+      for (int j = 0; j < int(kStep); ++j) {
+        const uint64_t v = q + j;
+        if (v < shift || v >= vend) continue;
+        g = (g << 1) + gear[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+        if (gear_zero<kHiOnly>(g, mask)) {
+          const unsigned long long k = atomicAdd(count, 1ull);
+          if (k < cap) out[k] = sg.vstart + (v - shift) + 1;
         }
       }
     }
@@ -204,6 +311,22 @@ hipError_t zg_cdc_candidates(const uint8_t* data, uint64_t n, uint64_t mask, uin
   else
     hipLaunchKernelGGL(k_cdc_candidates<false>, dim3(uint32_t((segs + 255) / 256)), dim3(256), 0, stream, data, n,
                        mask, out, count, capacity);
+  return hipGetLastError();
+}
+
+hipError_t zg_cdc_candidates_segs(const ZgSeg* segs, const uint64_t* win_prefix, uint32_t n_segs, uint64_t n_windows,
+                                  uint8_t* lead, uint64_t mask, uint64_t* out, unsigned long long* count,
+                                  uint64_t capacity, hipStream_t stream) {
+  if (n_segs == 0 || n_windows == 0) return hipSuccess;
+  const uint64_t blocks = (n_windows + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_seg_lead, dim3(n_segs), dim3(64), 0, stream, segs, lead);
+  if ((mask & 0xFFFFFFFFull) == 0)
+    hipLaunchKernelGGL(k_cdc_candidates_segs<true>, dim3(uint32_t(blocks)), dim3(256), 0, stream, segs, win_prefix,
+                       n_segs, lead, mask, out, count, capacity);
+  else
+    hipLaunchKernelGGL(k_cdc_candidates_segs<false>, dim3(uint32_t(blocks)), dim3(256), 0, stream, segs, win_prefix,
+                       n_segs, lead, mask, out, count, capacity);
   return hipGetLastError();
 }
 

@@ -258,6 +258,42 @@ size_t zg_dedup_table_bytes(uint64_t rows);
 hipError_t zg_dedup_chunks(const uint8_t* index, uint32_t m, const uint8_t* fresh, uint32_t n, uint32_t* table,
                            size_t table_bytes, int64_t* first, hipStream_t stream);
 
+// K14 (synth.hip): K5 over a file that exists only as a list of segments.  segs[i] = `len` > 0 bytes
+// at the absolute device address `addr` (any alignment) that are bytes [vstart, vstart + len) of the
+// file; the table is sorted and covers [0, n) without gaps.  A lane owns one 2 KiB window of a
+// segment's 16-byte-aligned address space; win_prefix[i] (n_segs + 1 entries) = windows of the
+// segments before i, window count of segment i = ceil(((addr & 15) + len) / 2048), n_windows =
+// win_prefix[n_segs].  lead: 64 * n_segs bytes of scratch; a pre-pass launch fills row i with the
+// min(64, vstart) file bytes before segment i, from which the segment's first window warms up (at
+// the start of the file there is no history).  out / count / capacity as zg_cdc_candidates: unsorted
+// END offsets (i + 1) in file coordinates, *count may exceed capacity (retry with more).  The set
+// equals zg_cdc_candidates' over the concatenated bytes.  Loads touch only aligned 16-byte blocks
+// that hold a byte of a segment: no pad behind a segment is assumed.  The caller vouches for the
+// table: nothing is checked on the device.  Two launches whatever n_segs is.
+typedef struct ZgSeg {
+  uint64_t addr;
+  uint64_t len;
+  uint64_t vstart;
+} ZgSeg;
+hipError_t zg_cdc_candidates_segs(const ZgSeg* segs, const uint64_t* win_prefix, uint32_t n_segs, uint64_t n_windows,
+                                  uint8_t* lead, uint64_t mask, uint64_t* out, unsigned long long* count,
+                                  uint64_t capacity, hipStream_t stream);
+
+// Chunk hashes at absolute addresses (blake3_flat.hip): K12 without the copy.  Record i hashes `len`
+// bytes at the device address `src` (any alignment, any allocation) and writes the Xet chunk hash to
+// hashes + 32 * `index` and, when sizes is non-null, `len` to sizes[`index`].  Rows no record names
+// keep their bytes; nothing but the two tables (and scratch) is stored.  Loads stay inside the
+// aligned dwords that hold a byte of the chunk.  len == 0 gives the empty hash; len > 128 KiB must be
+// refused by the caller (it hashes as empty).  scratch: zg_hash_scratch_bytes(n, sum of len).  The
+// caller vouches for every record.
+typedef struct ZgHashAt {
+  uint64_t src;    // device address of the chunk's bytes
+  uint32_t len;    // bytes (<= 128 KiB)
+  uint32_t index;  // row of hashes / sizes
+} ZgHashAt;
+hipError_t zg_hash_chunks_at(const ZgHashAt* recs, int n, uint8_t* hashes, uint64_t* sizes, uint8_t* scratch,
+                             size_t scratch_bytes, hipStream_t stream);
+
 int zg_device_count(void);
 // K6: out[i] (20 B) = SHA1("zest-xet-v1:" || hashes[i] (32 B)); out must be 4-byte aligned.
 hipError_t zg_sha1_info_hash(const uint8_t* hashes, int n, uint8_t* out, hipStream_t stream);

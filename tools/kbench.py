@@ -41,6 +41,33 @@ def emit(**kw):
     print(json.dumps(kw), flush=True)
 
 
+def loose_layout(total: int, model: str = "llama-3.1-8b", max_tensor: int = 256 << 20) -> list:
+    """[(name, bytes)] of `model`'s tensors in file order up to `total` bytes, the embeddings and
+    other tensors over `max_tensor` left out and the last one cut to fit: the sizes a trainer holds as
+    loose parameters (for 8B: 112 / 32 / 8 MiB projections and 8 KiB norms)."""
+    from zest_amd import models
+
+    out, left = [], total
+    for t in models.get(model).tensors:
+        if t.nbytes > max_tensor or not left:
+            continue
+        k = min(t.nbytes, left)
+        out.append((t.name, k))
+        left -= k
+    return out
+
+
+def loose_tensors(layout, dev, seed: int = 14) -> dict:
+    """Each tensor of `layout` as its own allocation, a uint8 view starting at a staggered 0..15
+    bytes after a 16-byte boundary and ending with the allocation's last byte (no pad), random bytes."""
+    out = {}
+    for i, (name, k) in enumerate(layout):
+        t = torch.empty(k + i % 16, dtype=torch.uint8, device=dev)[i % 16:]
+        ops.fill_synthetic(t, seed, sum(b for _, b in layout[:i]), 0)
+        out[name] = t
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -573,6 +600,87 @@ def main():
         k = m // 2
         assert torch.equal(dst12[int(d_off[k]):int(d_off[k] + ln[k])], src12[int(s_off[k]):int(s_off[k] + ln[k])])
         del src12, dst12, flat12, rec_d
+
+    if want("cdc_segments") or want("hash_chunks_at"):
+        # K14 and the hash at absolute addresses over 1 GiB of loose tensors (Llama-3.1-8B sizes, each
+        # its own allocation at a staggered 0..15 misalignment, no pad), next to K5 / K1 over the packed
+        # copy of the same bytes in the same process.  Every iteration is timed on its own, alternating:
+        # the spread of K5's (K1's) own iterations is the noise to read the difference against.
+        from zest_amd.publish import classify_chunks
+
+        lay = loose_layout(1 << 30)
+        ts14 = list(loose_tensors(lay, dev).values())
+        nb = sum(k for _, k in lay)
+        packed = ops.padded_empty(nb, dev)
+        at = 0
+        for t in ts14:
+            packed[at:at + t.numel()].copy_(t)
+            at += t.numel()
+        addrs = np.asarray([t.data_ptr() for t in ts14], dtype=np.uint64)
+        seg_lens = np.asarray([t.numel() for t in ts14], dtype=np.uint64)
+        cap = nb // 1024
+        cand = torch.empty(cap, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+
+        def spread(rows, **kw):
+            ms = {name: [] for name, _ in rows}
+            for _ in range(a.iters):
+                for name, fn in rows:
+                    ms[name].append(timed(fn, 1))
+            for name, v in ms.items():
+                emit(kernel=name, bytes=nb, ms=[round(x, 4) for x in v], ms_min=min(v), ms_max=max(v),
+                     ms_median=float(np.median(v)), gbps=nb / float(np.median(v)) / 1e6, **kw)
+            (x, _), (y, _) = rows
+            emit(ratio=f"{x} / {y}", median=float(np.median(ms[x]) / np.median(ms[y])),
+                 best=min(ms[x]) / min(ms[y]))
+
+        if want("cdc_segments"):
+            seg, wpre = ops.segment_table(addrs, seg_lens)
+            s = len(seg)
+            tab = np.zeros(ops.SEG_DTYPE.itemsize * s + 8 * (s + 1) + 64 * s, dtype=np.uint8)
+            tab[:ops.SEG_DTYPE.itemsize * s] = seg.view(np.uint8)
+            tab[ops.SEG_DTYPE.itemsize * s:ops.SEG_DTYPE.itemsize * s + 8 * (s + 1)] = wpre.view(np.uint8)
+            tab_d = torch.from_numpy(tab).to(dev)
+            p_pre = tab_d.data_ptr() + ops.SEG_DTYPE.itemsize * s
+
+            def run_k14():
+                cnt.zero_()
+                H.cdc_candidates_segs(tab_d.data_ptr(), p_pre, s, int(wpre[-1]), p_pre + 8 * (s + 1), ops.XET_MASK,
+                                      cand.data_ptr(), cnt.data_ptr(), cap, st)
+
+            def run_k5():
+                cnt.zero_()
+                H.cdc_candidates(packed.data_ptr(), nb, ops.XET_MASK, cand.data_ptr(), cnt.data_ptr(), cap, st)
+
+            spread((("cdc_candidates_segs[K14, loose]", run_k14), ("cdc_candidates[K5, packed]", run_k5)),
+                   segments=s, windows=int(wpre[-1]))
+            assert np.array_equal(ops.cdc_candidates_segments(ts14), ops.cdc_candidates(packed))
+
+        if want("hash_chunks_at"):
+            ends = ops.select_chunks(ops.cdc_candidates(packed), nb)
+            ln = np.diff(np.concatenate([[0], ends]).astype(np.uint64)).astype(np.uint32)
+            m = len(ln)
+            cl = classify_chunks(seg_lens, ends)
+            arena = ops.padded_empty(max(cl["seam_bytes"], 1), dev)
+            for sg, so, k, do in zip(cl["piece_seg"].tolist(), cl["piece_off"].tolist(), cl["piece_len"].tolist(),
+                                     cl["piece_dst"].tolist()):
+                arena[do:do + k].copy_(ts14[sg][so:so + k])
+            src = addrs[cl["seg"]] + cl["off"]
+            src[cl["seam"]] = np.uint64(arena.data_ptr()) + cl["arena_off"][cl["seam"]]
+            rec = np.empty(m, dtype=ops.HASH_AT_DTYPE)
+            rec["src"], rec["len"], rec["index"] = src, ln, np.arange(m)
+            rec_d = torch.from_numpy(rec.view(np.uint8)).to(dev)
+            o_d = torch.from_numpy((np.cumsum(ln, dtype=np.uint64) - ln).view(np.int64)).to(dev)
+            l_d = torch.from_numpy(ln.view(np.int32)).to(dev)
+            h_at = torch.zeros((m, 32), dtype=torch.uint8, device=dev)
+            h_rg = torch.zeros((m, 32), dtype=torch.uint8, device=dev)
+            sp, sb = ops.HashScratch(dev).get(m, nb)
+            spread((("hash_chunks_at[loose]", lambda: H.hash_chunks_at(rec_d.data_ptr(), m, h_at.data_ptr(), 0, sp, sb, st)),
+                    ("hash_ranges[packed]", lambda: H.hash_ranges(packed.data_ptr(), o_d.data_ptr(), l_d.data_ptr(), m,
+                                                                  h_rg.data_ptr(), 0, st, sp, sb))),
+                   chunks=m, seam_chunks=cl["seam_chunks"], seam_bytes=cl["seam_bytes"])
+            assert torch.equal(h_at, h_rg)
+        del ts14, packed
 
     if want("h2d"):
         pin = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()

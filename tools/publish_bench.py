@@ -14,6 +14,15 @@ Publisher and puller share one GPU and one process here, and the plain pull's ol
 the seeder over loopback: read the ratio as "bytes not moved", as for tools/delta_bench.py.
 
     python tools/publish_bench.py [--mb 1024] [--files 4] [--changed 0.05] [--rounds 2]
+
+`--loose`: the write side for a producer that holds loose tensors.  `--mb` of random bytes laid out
+as Llama-3.1-8B-shaped tensors (tools/kbench.py loose_layout: each its own allocation at a staggered
+misalignment) are published as a `TensorFile`, and, in the same run, through the route this
+replaces: `pack_safetensors` + `publish` of the packed buffer.  Alternated `--rounds` times after a
+warm-up of each; one JSON line per publish with the phase times and the peak of
+torch.cuda.max_memory_allocated above what was allocated before the call.
+
+    python tools/publish_bench.py --loose [--mb 1024] [--rounds 3]
 """
 from __future__ import annotations
 
@@ -52,6 +61,43 @@ def rounded(d: dict) -> dict:
             for k, v in d.items()}
 
 
+def loose(a) -> int:
+    from kbench import loose_layout, loose_tensors
+    from zest_amd.publish import TensorFile, pack_safetensors
+
+    dev = torch.device(a.device)
+    tensors = loose_tensors(loose_layout(a.mb << 20), dev)
+    sync = lambda: torch.cuda.synchronize(dev)
+
+    def packed_route(st):
+        return publish({"model.safetensors": pack_safetensors(tensors)}, stats=st)
+
+    def loose_route(st):
+        return publish({"model.safetensors": TensorFile(tensors)}, stats=st)
+
+    routes = (("loose[TensorFile]", loose_route), ("packed[pack_safetensors+publish]", packed_route))
+    manifests = {}
+    for rnd in range(-1, a.rounds):  # round -1 warms allocator and kernels up
+        for name, fn in routes:
+            sync()
+            torch.cuda.reset_peak_memory_stats(dev)
+            before, st = torch.cuda.memory_allocated(dev), {}
+            t0 = time.perf_counter()
+            pub = fn(st)
+            sync()
+            dt = time.perf_counter() - t0
+            peak = torch.cuda.max_memory_allocated(dev) - before
+            manifests[name] = pub.manifest
+            del pub
+            if rnd >= 0:
+                print(json.dumps(rounded({"step": "publish", "route": name, "round": rnd, "s": dt,
+                                          "file_gbps": st["bytes"] / dt / 1e9, "peak_bytes_above_start": peak,
+                                          "tensors": len(tensors), **st})), flush=True)
+    (x, _), (y, _) = routes
+    assert manifests[x] == manifests[y], "the two routes published different revisions"
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=int, default=1024)
@@ -59,7 +105,10 @@ def main() -> int:
     ap.add_argument("--changed", type=float, default=0.05)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--loose", action="store_true", help="loose tensors as a TensorFile against pack + publish")
     a = ap.parse_args()
+    if a.loose:
+        return loose(a)
     rng = np.random.default_rng(1)
     per = (a.mb << 20) // a.files // 2 * 2
     hub = FakeHub(policy="none")

@@ -203,10 +203,10 @@ def publish(files, **kw):
 
 
 def __getattr__(name: str):
-    if name == "ChunkIndex":  # lazy: importing the package does not import torch
-        from .publish import ChunkIndex
+    if name in ("ChunkIndex", "TensorFile"):  # lazy: importing the package does not import torch
+        from . import publish as _pub
 
-        return ChunkIndex
+        return getattr(_pub, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -825,12 +825,12 @@ def _check_reuse(src, lens, offs, index, dst_n: int, rows: int, buffers) -> None
         raise ValueError(f"{what}record {i}: index {int(index[i])} is also record {j}'s")
 
 
-def _u64(a, name: str) -> np.ndarray:
+def _u64(a, name: str, what: str = "reuse_chunks: ") -> np.ndarray:
     a = np.asarray(a).reshape(-1)
     if a.dtype.kind not in "ui" and len(a):
-        raise ValueError(f"reuse_chunks: {name} must be integers")
+        raise ValueError(f"{what}{name} must be integers")
     if a.dtype.kind == "i" and (a < 0).any():
-        raise ValueError(f"reuse_chunks: {name} must not be negative")
+        raise ValueError(f"{what}{name} must not be negative")
     return a.astype(np.uint64)
 
 
@@ -911,6 +911,218 @@ def reuse_chunks(src_addrs, lens, dst: torch.Tensor, dst_offs, hashes: torch.Ten
     for a, b, _ in parts:  # one stream: the launches run in order and share the scratch
         H.reuse_chunks(tab.data_ptr() + a * REUSE_DTYPE.itemsize, b - a, dst.data_ptr(), hashes.data_ptr(), sz,
                        scratch.data_ptr(), sb, st)
+
+
+# ----------------------------------------------------------------------------------------------
+# Chunk hashes at absolute addresses (K12 without the copy) and K14, CDC over a segment list
+# ----------------------------------------------------------------------------------------------
+HASH_AT_DTYPE = np.dtype([("src", "<u8"), ("len", "<u4"), ("index", "<u4")])
+SEG_DTYPE = np.dtype([("addr", "<u8"), ("len", "<u8"), ("vstart", "<u8")])
+CDC_WINDOW = 2048  # kSeg in csrc/gpu/synth.hip: bytes of aligned address space per lane
+
+
+def _outside_buffers(src: np.ndarray, lens: np.ndarray, buffers) -> np.ndarray:
+    """Mask of the ranges [src, src + lens) with lens > 0 that lie inside none of `buffers`, in
+    O((ranges + buffers) log buffers): with the buffers sorted by start and e[k] the largest end among
+    the first k + 1 of them, a range lies inside some buffer exactly when the largest end among the
+    buffers that start at or before src reaches src + lens.  Buffers may overlap or alias; two that
+    merely touch do not add up."""
+    if not len(buffers):
+        return lens > 0
+    b0 = np.asarray([t.data_ptr() for t in buffers], dtype=np.uint64)
+    b1 = b0 + np.asarray([t.numel() * t.element_size() for t in buffers], dtype=np.uint64)
+    order = np.argsort(b0, kind="stable")
+    b0, b1 = b0[order], np.maximum.accumulate(b1[order])
+    k = np.searchsorted(b0, src, side="right")  # buffers that start at or before src
+    end = b1[np.maximum(k, 1) - 1]
+    inside = (k > 0) & (src <= end) & (lens <= end - np.minimum(src, end))
+    return (lens > 0) & ~inside
+
+
+def hash_chunks_at(src_addrs, lens, hashes: torch.Tensor, hash_index, sizes=None, buffers=(), stream=None) -> None:
+    """Hash chunks where they lie: `reuse_chunks` without the copy (zg_hash_chunks_at,
+    csrc/gpu/blake3_flat.hip).
+
+    Record i hashes lens[i] bytes at the absolute address src_addrs[i] (any alignment), writes their
+    Xet chunk hash to hashes[hash_index[i]] (uint8 [N, 32]) and lens[i] to sizes[hash_index[i]]
+    (int64 [N], optional).  Rows no record names keep their values; the source bytes are only read,
+    and never past the aligned dwords that hold a byte of the chunk, so a chunk may end on the last
+    byte of its allocation.  A table is refused here (ValueError naming the record) unless every chunk
+    lies inside one of `buffers` (the tensors that vouch for the memory, on the device of `hashes`),
+    indices are unique rows of the tables and no chunk is over 128 KiB.  GPU tensors: asynchronous on
+    `stream` (default: the current stream), one launch per REUSE_LAUNCH_BYTES of chunks; CPU tensors
+    (host addresses): a NumPy path with the same hashes."""
+    what = "hash_chunks_at: "
+    src, lens, index = (_u64(a, k, what) for a, k in ((src_addrs, "src_addrs"), (lens, "lens"),
+                                                      (hash_index, "hash_index")))
+    n = len(src)
+    if not (len(lens) == len(index) == n):
+        raise ValueError(f"{what}src_addrs, lens and hash_index must be equally long")
+    if hashes.dtype != torch.uint8 or hashes.dim() != 2 or hashes.shape[1] != 32 or not hashes.is_contiguous():
+        raise ValueError(f"{what}hashes must be a contiguous uint8 [N, 32] tensor")
+    rows = hashes.shape[0]
+    if sizes is not None and (sizes.dtype != torch.int64 or sizes.dim() != 1 or sizes.shape[0] != rows
+                              or not sizes.is_contiguous()):
+        raise ValueError(f"{what}sizes must be a contiguous int64 [N] tensor as long as hashes")
+    dev = hashes.device
+    if sizes is not None and sizes.device != dev:
+        raise ValueError(f"{what}sizes is on {sizes.device}, hashes on {dev}")
+    buffers = list(buffers)
+    for k, t in enumerate(buffers):
+        if t.device != dev:
+            raise ValueError(f"{what}buffer {k} is on {t.device}, hashes on {dev}")
+
+    def first(mask):
+        return int(np.flatnonzero(mask)[0])
+
+    if (lens > MAX_CHUNK).any():
+        i = first(lens > MAX_CHUNK)
+        raise ValueError(f"{what}record {i}: len {int(lens[i])} is over the chunk maximum of {MAX_CHUNK} bytes")
+    out = _outside_buffers(src, lens, buffers)
+    if out.any():
+        i = first(out)
+        raise ValueError(f"{what}record {i}: chunk [{int(src[i]):#x}, {int(src[i] + lens[i]):#x}) lies outside "
+                         "every buffer")
+    if (index >= np.uint64(rows)).any():
+        i = first(index >= np.uint64(rows))
+        raise ValueError(f"{what}record {i}: index {int(index[i])} is past the table ({rows} rows)")
+    order = np.argsort(index, kind="stable")
+    dup = index[order][1:] == index[order][:-1]
+    if dup.any():
+        k = first(dup)
+        i, j = int(order[k + 1]), int(order[k])
+        raise ValueError(f"{what}record {i}: index {int(index[i])} is also record {j}'s")
+    if n == 0:
+        return
+    if dev.type != "cuda":
+        import ctypes
+
+        for a, ln, r in zip(src.tolist(), lens.tolist(), index.tolist()):
+            data = ctypes.string_at(a, ln) if ln else b""
+            hashes[r] = torch.from_numpy(np.frombuffer(_core.chunk_hash(data), dtype=np.uint8).copy())
+            if sizes is not None:
+                sizes[r] = ln
+        return
+    H = hip()
+    assert H.HASH_AT_BYTES == HASH_AT_DTYPE.itemsize, "ZgHashAt layout drift"
+    if hashes.data_ptr() % 16:
+        raise ValueError(f"{what}hashes must be 16-byte aligned")
+    rec = np.empty(n, dtype=HASH_AT_DTYPE)
+    rec["src"], rec["len"], rec["index"] = src, lens, index
+    cum = np.cumsum(lens, dtype=np.uint64)
+    cuts = [0] + (np.flatnonzero(np.diff(cum // np.uint64(REUSE_LAUNCH_BYTES))) + 1).tolist() + [n]
+    parts = [(a, b, int(lens[a:b].sum(dtype=np.uint64))) for a, b in zip(cuts, cuts[1:]) if b > a]
+    sb = max(H.hash_scratch_bytes(b - a, tot) for a, b, tot in parts)
+
+    def alloc():
+        return _dev_array(rec, dev), torch.empty(sb, dtype=torch.uint8, device=dev)
+
+    if stream is None:
+        st = _stream(dev)
+        tab, scratch = alloc()
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the uploads and frees are ordered on the launch's stream
+            tab, scratch = alloc()
+    sz = sizes.data_ptr() if sizes is not None else 0
+    for a, b, _ in parts:  # one stream: the launches run in order and share the scratch
+        H.hash_chunks_at(tab.data_ptr() + a * HASH_AT_DTYPE.itemsize, b - a, hashes.data_ptr(), sz,
+                         scratch.data_ptr(), sb, st)
+
+
+def _flat_u8(t: torch.Tensor) -> torch.Tensor:
+    """The bytes of a contiguous tensor as a 1-D uint8 view of the same memory."""
+    return t.reshape(-1).view(torch.uint8)
+
+
+def segment_table(addrs, lens) -> tuple[np.ndarray, np.ndarray]:
+    """K14's host tables for segments at `addrs` of `lens` > 0 bytes, in file order: the SEG_DTYPE
+    records (vstart = running sum of the lengths) and the prefix count of 2 KiB windows of each
+    segment's 16-byte-aligned address space (len + 1 entries, the last is the launch's lane count)."""
+    addrs, lens = np.asarray(addrs, dtype=np.uint64), np.asarray(lens, dtype=np.uint64)
+    seg = np.empty(len(addrs), dtype=SEG_DTYPE)
+    seg["addr"], seg["len"] = addrs, lens
+    seg["vstart"] = np.cumsum(lens, dtype=np.uint64) - lens
+    wins = ((addrs & np.uint64(15)) + lens + np.uint64(CDC_WINDOW - 1)) // np.uint64(CDC_WINDOW)
+    return seg, np.concatenate([np.zeros(1, np.uint64), np.cumsum(wins, dtype=np.uint64)])
+
+
+def cdc_candidates_segments(segments, mask: int = XET_MASK, capacity: int | None = None, buffers=()) -> np.ndarray:
+    """`cdc_candidates` of a file that exists only as a list of segments: K14 (zg_cdc_candidates_segs,
+    csrc/gpu/synth.hip).  Sorted END offsets (i + 1), in the coordinates of the concatenation, whose
+    gear hash over the concatenated bytes has (h & mask) == 0: the same set `cdc_candidates` gives for
+    the packed bytes, for any mask.
+
+    segments: a list of contiguous tensors on one device, each read where it lies (any alignment, no
+    pad behind it: loads touch only aligned 16-byte blocks that hold a byte of a segment; zero-element
+    tensors are skipped), or `(addrs, lens)` arrays of absolute addresses and lengths > 0 with
+    `buffers`, the tensors that vouch for the memory: every segment must lie inside one of them.  One
+    table upload, two launches and one count read-back whatever the number of segments; a capacity
+    that turns out too small is retried with the count the kernel reported.  CPU tensors are
+    concatenated and scanned by `cdc_candidates`' host path."""
+    what = "cdc_candidates_segments: "
+    if isinstance(segments, tuple) and len(segments) == 2 and not isinstance(segments[0], torch.Tensor):
+        addrs, lens = _u64(segments[0], "addrs", what), _u64(segments[1], "lens", what)
+        buffers = list(buffers)
+        if len(addrs) != len(lens):
+            raise ValueError(f"{what}addrs and lens must be equally long")
+        if (lens == 0).any():
+            raise ValueError(f"{what}segment {int(np.flatnonzero(lens == 0)[0])} is empty: leave empty segments out")
+        if not buffers and len(addrs):
+            raise ValueError(f"{what}address segments need buffers= that vouch for the memory")
+        out = _outside_buffers(addrs, lens, buffers)
+        if out.any():
+            i = int(np.flatnonzero(out)[0])
+            raise ValueError(f"{what}segment {i}: [{int(addrs[i]):#x}, {int(addrs[i] + lens[i]):#x}) lies outside "
+                             "every buffer")
+        devs = {t.device for t in buffers}
+        keep, by_addr = buffers, True
+    else:
+        segs = list(segments)
+        for i, t in enumerate(segs):
+            if not isinstance(t, torch.Tensor) or not t.is_contiguous():
+                raise ValueError(f"{what}segment {i} must be a contiguous tensor (or pass (addrs, lens) and buffers=)")
+        devs = {t.device for t in segs}
+        keep, by_addr = [_flat_u8(t) for t in segs if t.numel()], False
+        addrs = np.asarray([t.data_ptr() for t in keep], dtype=np.uint64)
+        lens = np.asarray([t.numel() for t in keep], dtype=np.uint64)
+    if len(devs) > 1:
+        raise ValueError(f"{what}segments on more than one device ({', '.join(sorted(map(str, devs)))})")
+    if len(addrs) == 0:
+        return np.zeros(0, dtype=np.uint64)
+    dev = devs.pop()
+    if dev.type != "cuda":
+        if by_addr:
+            import ctypes
+
+            data = b"".join(ctypes.string_at(a, ln) for a, ln in zip(addrs.tolist(), lens.tolist()))
+            return cdc_candidates(torch.frombuffer(bytearray(data), dtype=torch.uint8), mask)
+        return cdc_candidates(torch.cat(keep), mask)
+    H = hip()
+    assert H.SEG_BYTES == SEG_DTYPE.itemsize, "ZgSeg layout drift"
+    seg, wpre = segment_table(addrs, lens)
+    s, n = len(seg), int(lens.sum(dtype=np.uint64))
+    # one upload: [segments | window prefix | room for the 64-byte lead-in rows the pre-pass fills]
+    host = np.zeros(SEG_DTYPE.itemsize * s + 8 * (s + 1) + 64 * s, dtype=np.uint8)
+    host[:SEG_DTYPE.itemsize * s] = seg.view(np.uint8)
+    host[SEG_DTYPE.itemsize * s:SEG_DTYPE.itemsize * s + 8 * (s + 1)] = wpre.view(np.uint8)
+    with torch.cuda.device(dev):
+        tab = torch.from_numpy(host).to(dev)
+        p_seg = tab.data_ptr()
+        p_pre = p_seg + SEG_DTYPE.itemsize * s
+        p_lead = p_pre + 8 * (s + 1)
+        cap = capacity or max(1024, n // 4096)
+        while True:
+            out = torch.empty(cap, dtype=torch.int64, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            H.cdc_candidates_segs(p_seg, p_pre, s, int(wpre[-1]), p_lead, mask, out.data_ptr(), count.data_ptr(), cap,
+                                  _stream(dev))
+            k = int(count.item())
+            if k <= cap:
+                break
+            cap = k + 1024  # overflow: the kernel counted every candidate, so the retry fits
+        del keep  # the segments were alive until the read-back above
+        return np.sort(out[:k].cpu().numpy().astype(np.uint64))
 
 
 # ----------------------------------------------------------------------------------------------
