@@ -190,13 +190,24 @@ __global__ void __launch_bounds__(kScanThreads) k_hdr_scan(const uint8_t* __rest
 // raw-header look-alikes ([00 x y z 00 x y z], clen == ulen) per 256 MiB, so demanding exactly
 // n_chunks candidates sent every term of a 256 MiB batch back to the serial walk.  The chain is
 // instead picked out of the candidate set G' = {candidates with a successor (a candidate, or the
-// run's end) that sit at offset 0 or are some candidate's successor}.  If G' contains offset 0, is
-// closed under the successor, and has exactly n_chunks members, it IS the true chain: the true
-// chain starts at 0 and follows successors, so closure puts all of it in G', and the count leaves
-// room for nothing else.  Otherwise the serial walk decides (records and error codes stay exactly
-// walk_term's).
+// run's end) that sit at offset 0 or are some candidate's successor}.  G' is accepted when
+//   (a) it contains offset 0,
+//   (b) it is closed under the successor (a member's successor is a member, or the run's end),
+//   (c) every member other than offset 0 is the successor of a MEMBER (kChain), and
+//   (d) it has n_chunks members whose sizes add up to the term's ulen (when that is given).
+// Then G' is exactly the chain from offset 0: a successor lies strictly behind its candidate, so by
+// (c) every member leads back through members at ever smaller offsets, which can only stop at
+// offset 0; a candidate has one successor, so the forward path from 0 is unique and every member
+// lies on it; and by (a) and (b) that path stays in G' until it hits the run's end.  (Without (c) a
+// look-alike outside G' could put its successor Y into G': Y is pointed at, though not from the
+// chain, and made up the count of a run one chunk short of the plan.)  Every member passed
+// plausible_header, which implies walk_term's header, range and capacity checks, so with (d) the
+// serial walk would write these very records and report nothing.  Otherwise -- and for a chain
+// holding a chunk the scan does not list, such as a raw chunk of zero bytes -- the serial walk
+// decides: records and error codes are walk_term's in every case.
 constexpr uint32_t kEnd = 0xFFFFFFFEu, kNone = 0xFFFFFFFFu;
-constexpr uint32_t kPointed = 1u << 31, kGood = 1u << 30;
+// flags in cs[] above clen (24 bits) and the scheme (2 bits)
+constexpr uint32_t kPointed = 1u << 31, kGood = 1u << 30, kChain = 1u << 29;
 constexpr uint32_t kFellBack = 1u << 31;  // in counts[t] after the link: term t took the serial walk
 
 __device__ __forceinline__ uint32_t lds_find(const uint32_t* key, uint32_t n, uint32_t v) {
@@ -271,8 +282,14 @@ __global__ void __launch_bounds__(kLinkThreads) k_hdr_link(const uint8_t* __rest
   for (uint32_t i = tid; i < n; i += kLinkThreads)
     if (nx[i] != kNone && (key[i] == 0 || (cs[i] & kPointed))) atomicOr(&cs[i], kGood);
   __syncthreads();
-  for (uint32_t i = tid; i < n; i += kLinkThreads)  // closed under the successor
-    if ((cs[i] & kGood) && nx[i] != kEnd && !(cs[nx[i]] & kGood)) ok = 0;
+  for (uint32_t i = tid; i < n; i += kLinkThreads)  // successors of members
+    if ((cs[i] & kGood) && nx[i] < n) atomicOr(&cs[nx[i]], kChain);
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += kLinkThreads) {
+    if (!(cs[i] & kGood)) continue;
+    if (nx[i] != kEnd && !(cs[nx[i]] & kGood)) ok = 0;  // closed under the successor
+    if (key[i] != 0 && !(cs[i] & kChain)) ok = 0;       // reached from a member
+  }
   if (tid == 0 && (key[0] != 0 || !(cs[0] & kGood))) ok = 0;
   // exclusive prefix sums (chunk count, uncompressed bytes) over the chain members: each thread
   // owns a contiguous slice, then a wave scan and the wave totals
@@ -327,7 +344,7 @@ __global__ void __launch_bounds__(kLinkThreads) k_hdr_link(const uint8_t* __rest
     ch.dst = tm.dst + off;
     ch.clen = cs[i] & 0xFFFFFF;
     ch.ulen = ul[i];
-    ch.scheme = (cs[i] >> 24) & 0x3F;
+    ch.scheme = (cs[i] >> 24) & 0x3;
     ch.term = uint32_t(t);
     chunks[tm.chunk_base + c] = ch;
     ++c;

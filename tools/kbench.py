@@ -343,19 +343,21 @@ def main():
         ingest_case("bf16_1g", raw, "bg4", 3, after=occ)
         del raw
 
-    if want("k3pair"):
+    if want("k3pair") or want("index"):
         # round 4: producer/consumer wave pairs (k_lz4_pair) vs the one-wave decoder, and the serial
         # header walk k_index_terms, at a small launch (256 MiB, ~4 k chunks: fewer chunks than wave
         # slots) and a bench round (1 GiB).  (A scan-based header walk measured here at 5.4 / 12.3 ms
         # against 0.51 / 0.61 ms serial was removed: profiles/r4/kbench_k3pair_r4b.jsonl.)
-        for m, tag in ((128 << 20, "bf16_128m"), (256 << 20, "bf16_256m"), (512 << 20, "bf16_512m"),
-                       (768 << 20, "bf16_768m"), (1 << 30, "bf16_1g")):
+        # `--only index`: just the header walks, serial and parallel (scan + link), at 256 MiB.
+        sizes = ((128 << 20, "bf16_128m"), (256 << 20, "bf16_256m"), (512 << 20, "bf16_512m"),
+                 (768 << 20, "bf16_768m"), (1 << 30, "bf16_1g"))
+        for m, tag in sizes if want("k3pair") else sizes[1:2]:
             w = (np.random.default_rng(0).standard_normal(m // 2).astype(np.float32) * 0.02)
             raw = (w.view(np.uint32) >> 16).astype(np.uint16).tobytes()
             del w
 
             def pair(src, dst, ws, n, m=m, tag=tag, raw=raw):
-                for label, kw in (("one-wave", {}), ("pair", {"pair": True})):
+                for label, kw in (("one-wave", {}), ("pair", {"pair": True})) if want("k3pair") else ():
                     dst.zero_()
                     ms = timed(lambda: H.lz4_decode(src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(),
                                                     ws.chunks.data_ptr(), n, ws.err.data_ptr(), st, 0, **kw), 5)
@@ -370,6 +372,15 @@ def main():
                 ops.raise_on_error(ws.err)
                 emit(kernel=f"index_terms({tag},serial)", bytes=src.numel(), ms=ms, gbps=src.numel() / ms / 1e6,
                      terms=nt, chunks=n, same_records=bool(torch.equal(ws.chunks, chunks0)))
+                sp, sb = ws.index_scratch(H, nt)
+                ws.chunks.zero_()
+                ms = timed(lambda: H.index_terms_scan(src.data_ptr(), src.numel(), ws.terms.data_ptr(), nt,
+                                                      ws.chunks.data_ptr(), ws.err.data_ptr(), sp, sb, st), 20)
+                ops.raise_on_error(ws.err)
+                fell_back = int((ws._index_scratch[:4 * nt].view(torch.int32) < 0).sum())
+                emit(kernel=f"index_terms({tag},scan)", bytes=src.numel(), ms=ms, gbps=src.numel() / ms / 1e6,
+                     terms=nt, chunks=n, fallback_terms=fell_back,
+                     same_records=bool(torch.equal(ws.chunks, chunks0)))
 
             ingest_case(tag, raw, "bg4", 3, after=pair)
             del raw

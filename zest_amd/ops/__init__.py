@@ -259,8 +259,10 @@ FUSED_INGEST = os.environ.get("ZEST_FUSED_INGEST", "1") != "0"
 # opt-in after it measured slower than the serial walk (gpubench 256 MiB lz4_decode_gpu 3.96 -> 9.69
 # ms, profiles/r5/gpubench256_scan_r5c.json): LZ4 streams of BG4 bf16 weights are full of header-like
 # byte patterns.  Compressed candidates now need the LZ4 frame magic (millions of candidates -> a
-# few), and the link picks the chain out of the candidates instead of handing any term with a
-# look-alike to the serial walk (which every term of a 256 MiB batch had): scan 112 us + link 32 us
+# few), and the link picks the chain from offset 0 out of the candidates (a chain member is offset 0
+# or a member's successor) instead of handing any term with a look-alike to the serial walk (which
+# every term of a 256 MiB batch had; it still decides whatever is not exactly that chain with the
+# planned count): scan 112 us + link 32 us
 # against the serial walk's 761 us; lz4_decode_gpu 69.0 -> 85.4 GB/s, xorb_verify_gpu 267 -> 575
 # GiB/s; the 70B engine bench is unchanged (64.34 / 64.30 GB/s serial / parallel: the walk is hidden
 # under each round's H2D copy either way) (profiles/r5/index_scan_r5ab/).
