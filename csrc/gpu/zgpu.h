@@ -197,6 +197,28 @@ enum {
 hipError_t zg_slice_gather(const uint8_t* src, const uint64_t* table, uint32_t n, uint64_t dst_total, uint8_t* dst,
                            hipStream_t stream);
 
+// K15 (scatter.hip): K10 with the destination at any address.  table: device block of
+// ZG_SCATTER_ROWS rows of n uint64 each.  Entry i is n_runs[i] runs of run_bytes[i] bytes, run r read
+// at src + src_off[i] + r * src_stride[i] (any alignment, src_stride >= run_bytes), laid end to end at
+// the absolute device address dst_addr[i] (any alignment, any allocation).  blk_end[i] is the
+// inclusive prefix sum of the entries' aligned 16-byte destination block counts,
+// ceil((dst_addr + size) / 16) - floor(dst_addr / 16) for size = n_runs * run_bytes > 0 and 0
+// otherwise; total_blocks = blk_end[n - 1].  Outputs are disjoint from each other and from src;
+// entries should be sorted by dst_addr (locality only); zero-size entries are legal.  Only output
+// bytes are stored, 16 bytes at a time only to aligned blocks wholly inside one output, and no
+// destination byte is read.  The caller vouches for the table: nothing is checked on the device.
+enum {
+  ZG_SCATTER_SRC_OFF = 0,
+  ZG_SCATTER_RUN_BYTES = 1,
+  ZG_SCATTER_SRC_STRIDE = 2,
+  ZG_SCATTER_N_RUNS = 3,
+  ZG_SCATTER_DST_ADDR = 4,
+  ZG_SCATTER_BLK_END = 5,
+  ZG_SCATTER_ROWS = 6
+};
+hipError_t zg_slice_scatter(const uint8_t* src, const uint64_t* table, uint32_t n, uint64_t total_blocks,
+                            hipStream_t stream);
+
 // K8: pull each segment's bytes from a peer's IPC-mapped arena (xGMI) into this GPU's arena;
 // every segment is read concurrently.  src[i] and dst[i] must be congruent mod 16.
 enum { kZgMaxPeerSegs = 16 };

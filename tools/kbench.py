@@ -565,6 +565,73 @@ def main():
             del out11, got11
         del out, flat, tab_d, views, got
 
+    if want("slice_scatter"):
+        # K15 slice_scatter on K10's table (the second Llama-3.1-70B shard, rank 0 of 8, then world 1:
+        # every tensor whole), each destination a separately allocated tensor, next to K10 into its
+        # arena in the same process and to the per-tensor dst.copy_(view) loop that into= replaces.
+        # With 16-byte-aligned destinations K15 and K10 do the same work: the expectation to test is
+        # parity.  Rows alternate, one timed launch per row and iteration; median and range per row.
+        from zest_amd import device as zdev
+        from zest_amd import models
+        from zest_amd.shard import Shard, plan_file
+
+        sf = models.get("llama-3.1-70b").shards()[1]
+        start, meta = zdev.parse_safetensors_header(sf.header)
+        fbuf = arena if n >= sf.size else ops.padded_empty(sf.size, dev)
+        if fbuf is not arena:
+            ops.fill_synthetic(fbuf, 2, 0, 0)
+        fbuf = fbuf[:sf.size]
+        views = zdev.tensor_views(fbuf, start, meta)
+        for world in (8, 1):
+            sh = Shard(0, world)
+            plan = plan_file(start, meta, sh, sf.size)
+            kept = sum(t.nbytes for t in plan.tensors)
+            out = ops.padded_empty(plan.arena_bytes, dev)
+            dests = [torch.empty(t.shape, dtype=zdev.ST_DTYPES[t.dtype], device=dev) for t in plan.tensors]
+            tab10 = np.empty((H.SLICE_ROWS, len(plan.table)), dtype=np.uint64)
+            for k, f in enumerate(ops.SLICE_DTYPE.names):
+                tab10[k] = plan.table[f]
+            tab10[5] = tab10[4] + tab10[1] * tab10[3]
+            tab10_d = torch.from_numpy(tab10.view(np.int64)).to(dev)
+            stab = np.empty(len(plan.table), dtype=ops.SCATTER_DTYPE)
+            for f in ops.SCATTER_DTYPE.names[:4]:
+                stab[f] = plan.table[f]
+            stab["dst_addr"] = [d.data_ptr() for d in dests]
+            tab15 = ops.scatter_soa(stab, stab["run_bytes"] * stab["n_runs"])
+            tab15_d = torch.from_numpy(tab15.view(np.int64)).to(dev)
+            srcs = []
+            for t in plan.tensors:
+                act = sh.resolve(t.name, meta[t.name]["shape"], t.dtype)
+                srcs.append(views[t.name] if act is None else views[t.name].narrow(act[0], act[1], act[2] - act[1]))
+
+            def copy_loop():
+                for d, s_ in zip(dests, srcs):
+                    d.copy_(s_)
+
+            rows = (("slice_scatter[kernel]", lambda: H.slice_scatter(fbuf.data_ptr(), tab15_d.data_ptr(), tab15.shape[1],
+                                                                      int(tab15[5, -1]), st)),
+                    ("slice_scatter[ops]", lambda: ops.slice_scatter(fbuf, stab, dests)),
+                    ("slice_gather[kernel]", lambda: H.slice_gather(fbuf.data_ptr(), tab10_d.data_ptr(), tab10.shape[1],
+                                                                    int(tab10[5, -1]), out.data_ptr(), st)),
+                    ("dst_copy_view_loop", copy_loop))
+            ms = {name: [] for name, _ in rows}
+            for _ in range(max(5, a.iters)):
+                for name, fn in rows:
+                    ms[name].append(timed(fn, 1))
+            for name, v in ms.items():
+                med = float(np.median(v))
+                emit(kernel=name, world=world, bytes=kept, ms=med, ms_min=min(v), ms_max=max(v), iters=len(v),
+                     gbps=kept / med / 1e6, file_bytes=sf.size, tensors=len(plan.tensors),
+                     dst_misaligned=sum(d.data_ptr() % 16 != 0 for d in dests))
+            for d in dests:
+                d.zero_()
+            rows[0][1]()  # the kernel row alone refills the destinations: compare with K10's arena
+            got = plan.views(out)
+            for t, d in zip(plan.tensors, dests):
+                assert torch.equal(got[t.name].view(torch.uint8), d.view(torch.uint8)), t.name
+            del out, dests, tab10_d, tab15_d, srcs, got
+        del views
+
     if want("reuse_chunks"):
         # K12 reuse_chunks: 1 GiB of CDC-sized chunks (the size mix of 64 MiB of the arena's own bytes,
         # repeated) at random source and destination misalignments, next to the two passes it fuses, built

@@ -58,7 +58,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
          group=None, repo_type: str = "model", verbose: bool = False, direct: bool | None = None,
          save_snapshot: bool = False, threads: int = 16, staging_bytes: int = 1 << 30, stats: dict | None = None,
          exchange: str = "auto", round_bytes: int | None = None, seed=False, shard=None,
-         scratch_bytes: int | None = None, base=None):
+         scratch_bytes: int | None = None, base=None, into=None, strict: bool = True):
     """Download `repo@revision` via zest.
 
     * default: returns the HF-cache snapshot directory (reference behaviour).
@@ -113,7 +113,45 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       owner, then all-to-all; any backend, CPU groups).  ZEST_SHARD_CROSSCHECK=1 runs both and compares
       every kept byte.  `stats["shard"]` also receives exchange, rounds, owned_files, fetched_bytes,
       received_bytes and p2p_ratio.  seed=, save_snapshot=True and direct=False stay refused.
+    * into=target (a {checkpoint tensor name: destination tensor} dict or a torch.nn.Module, taken as
+      its state_dict(keep_vars=True)), device="cuda:N" / "cpu" direct pulls: the tensors are written into
+      memory the caller already owns, at fixed addresses, instead of into new buffers (zest_amd.into).
+      Files are pulled and verified whole through the reused scratch of `scratch_bytes`, as with
+      shard=, then ops.slice_scatter (kernel K15) copies each wanted tensor to its destination's address:
+      peak device memory is the model plus one scratch, not two models.  No byte of a file reaches a
+      destination before the whole file has passed its Xet hash; a file that fails, or whose tensors
+      differ from their destinations in dtype or shape (ValueError naming the tensor), leaves its
+      destinations untouched, while earlier files stay written.  Destinations are contiguous views
+      on `device` that do not overlap; a fused parameter is passed as one view per checkpoint tensor;
+      names that alias the same bytes (tied weights) are written once, under the first name.  With
+      shard= each destination holds the rank's slice.  Checkpoint tensors that `into` does not name
+      are not kept, and files that hold none of its names are not fetched.  strict=True (default):
+      KeyError after the pull when no file provided a wanted name.  Returns {name: the destination
+      passed in} for every tensor written, after the device has finished.  Autograd version counters
+      are not bumped, and the caller must not run the model during the call.  `stats["into"]`
+      receives file_bytes, written_bytes, tensors, skipped_files, missing, groups, scratch_bytes and
+      scatter_s.  Refused with device="all", base=, seed=, save_snapshot=True, direct=False and no
+      device.
     """
+    if into is not None:
+        if device is None:
+            raise ValueError("into= needs a device: use device='cuda:N' (or 'cpu'), the device the destinations are "
+                             "on; a snapshot pull has no tensors to place")
+        if device == "all":
+            raise ValueError("into= is not supported with device='all' (swarm pulls): run one process per GPU with "
+                             "device='cuda:N' and that GPU's own destinations")
+        if base is not None:
+            raise ValueError("into= is not supported with base=: nothing records yet which chunks the destinations "
+                             "hold; pull with base= into new tensors, or with into= without a base")
+        if seed is not False and seed is not None:
+            raise ValueError("into= is not supported with seed=: the file bytes do not stay resident as files; seed "
+                             "from a plain device pull")
+        if save_snapshot:
+            raise ValueError("into= is not supported with save_snapshot=True: whole files never stay in memory; "
+                             "write the snapshot with a plain pull(repo)")
+        if direct is False:
+            raise ValueError("into= is not supported with direct=False (the snapshot path): use the default "
+                             "device-direct pull, or load the snapshot and copy_ the tensors yourself")
     if base is not None:
         if device is None and not as_tensors:
             raise ValueError("base= needs a device pull: a snapshot pull lands on disk, where nothing is resident; use "
@@ -186,7 +224,8 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
                               dht_bootstrap=dht_bootstrap, repo_type=repo_type, save_snapshot=save_snapshot,
                               threads=threads, staging_bytes=staging_bytes, include=include, seed=seed, shard=shard,
                               scratch_bytes=scratch_bytes,
-                              stats=stats if shard is not None or base is not None else None, base=base)
+                              stats=stats if shard is not None or base is not None or into is not None else None,
+                              base=base, into=into, strict=strict)
     from .device import load_snapshot
 
     res = _client.pull_detailed(repo, revision, **kw)

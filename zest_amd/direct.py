@@ -28,6 +28,12 @@ keeps nothing (per `model.safetensors.index.json`) are not fetched.  It bounds d
 network bytes (the collective `pull(device="all", shard=...)`, zest_amd.parallel.shard_pull,
 does).  `stats["shard"]` receives file_bytes, kept_bytes, skipped_files, groups, scratch_bytes and
 gather_s.
+
+    pull_to_device("meta-llama/Llama-3.1-70B", "v2", device="cuda:0", into=model)
+
+`into=` (a {checkpoint tensor name: destination tensor} dict or a torch.nn.Module): the same flow,
+but after a group of files verifies `ops.slice_scatter` copies the wanted tensors to the addresses
+of tensors the caller already owns, so nothing but the scratch is allocated (zest_amd.into).
 """
 from __future__ import annotations
 
@@ -44,7 +50,23 @@ from . import shard as zshard
 def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: bool = True, peers=None,
                    tracker=None, dht: bool = True, dht_bootstrap=None, repo_type: str = "model",
                    save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False,
-                   shard=None, scratch_bytes: int | None = None, stats: dict | None = None, base=None):
+                   shard=None, scratch_bytes: int | None = None, stats: dict | None = None, base=None, into=None,
+                   strict: bool = True):
+    if into is not None:
+        if device is None:
+            raise ValueError("into= needs a device: use device='cuda:N' (or 'cpu'), the device the destinations are on")
+        if device == "all":
+            raise ValueError("into= is not supported with device='all' (swarm pulls): run one process per GPU with "
+                             "device='cuda:N' and that GPU's own destinations")
+        if base is not None:
+            raise ValueError("into= is not supported with base=: nothing records yet which chunks the destinations "
+                             "hold; pull with base= into new tensors, or with into= without a base")
+        if seed is not False and seed is not None:
+            raise ValueError("into= is not supported with seed=: the file bytes do not stay resident as files; seed "
+                             "from a plain device pull")
+        if save_snapshot:
+            raise ValueError("into= is not supported with save_snapshot=True: whole files never stay in memory; "
+                             "write the snapshot with a plain pull(repo)")
     if base is not None:
         if device is None:
             raise ValueError("base= needs a device: a delta pull copies resident chunks inside device='cuda:N' (or "
@@ -71,6 +93,12 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
     dev = torch.device(device)
     if dev.type not in ("cuda", "cpu"):
         raise ValueError("pull_to_device needs a GPU or the CPU")
+    if into is not None:
+        from .into import pull_into
+
+        return pull_into(repo, revision, dev, into, None if shard is None else zshard.as_shard(shard), scratch_bytes,
+                         stats, strict, p2p=p2p, peers=peers, tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap,
+                         repo_type=repo_type, staging_bytes=staging_bytes, threads=threads, include=include)
     if shard is not None:
         return _pull_sharded(repo, revision, dev, zshard.as_shard(shard), scratch_bytes, stats, p2p=p2p, peers=peers,
                              tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap, repo_type=repo_type,

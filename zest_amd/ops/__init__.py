@@ -7,7 +7,7 @@ CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/C
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
 K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers,
-K12 reuse_chunks, K13 dedup_chunks.
+K12 reuse_chunks, K13 dedup_chunks, K15 slice_scatter.
 """
 from __future__ import annotations
 
@@ -774,9 +774,127 @@ def _slice_gather_cpu(src: np.ndarray, table: np.ndarray, dst: np.ndarray) -> No
 
 
 # ----------------------------------------------------------------------------------------------
+# K15: scatter the kept slices of many tensors out of one file buffer to addresses the caller owns
+# ----------------------------------------------------------------------------------------------
+SCATTER_DTYPE = np.dtype([("src_off", "<u8"), ("run_bytes", "<u8"), ("src_stride", "<u8"), ("n_runs", "<u8"),
+                          ("dst_addr", "<u8")])
+MAX_SCATTER_ENTRIES = (1 << 32) - 1
+
+
+def _check_scatter_table(table, src: torch.Tensor, buffers) -> tuple[np.ndarray, np.ndarray]:
+    """Validate a scatter table against its source and the buffers that vouch for the destinations;
+    returns (table, output bytes per entry).  Every message names the entry by its index in `table`."""
+    what = "slice_scatter: "
+    n = table.size if isinstance(table, np.ndarray) else len(table)
+    if n > MAX_SCATTER_ENTRIES:  # before anything is copied: the kernel indexes entries with 32 bits
+        raise ValueError(f"{what}{n} entries, at most {MAX_SCATTER_ENTRIES}")
+    table = np.ascontiguousarray(table, dtype=SCATTER_DTYPE).reshape(-1)
+    so, rb, st, nr, da = ([int(x) for x in table[f]] for f in SCATTER_DTYPE.names)  # Python ints: no wrap-around
+    src_n = src.numel()
+    size = [rb[i] * nr[i] for i in range(len(table))]
+    for i, n in enumerate(size):
+        if n and st[i] < rb[i]:
+            raise ValueError(f"{what}entry {i}: src_stride {st[i]} < run_bytes {rb[i]}")
+        if n and so[i] + (nr[i] - 1) * st[i] + rb[i] > src_n:
+            raise ValueError(f"{what}entry {i}: runs reach past the source ({src_n} bytes)")
+        if n and da[i] + n > 1 << 64:
+            raise ValueError(f"{what}entry {i}: output [{da[i]:#x}, {da[i] + n:#x}) wraps around the address space")
+    sizes = np.asarray(size, dtype=np.uint64)
+    out = _outside_buffers(table["dst_addr"], sizes, buffers)
+    if out.any():
+        i = int(np.flatnonzero(out)[0])
+        raise ValueError(f"{what}entry {i}: output [{da[i]:#x}, {da[i] + size[i]:#x}) does not lie inside one buffer")
+    live = np.flatnonzero(sizes)
+    order = live[np.argsort(table["dst_addr"][live], kind="stable")]
+    for j, i in zip(order[:-1].tolist(), order[1:].tolist()):
+        if da[i] < da[j] + size[j]:
+            raise ValueError(f"{what}entry {max(i, j)}: output [{da[max(i, j)]:#x}, "
+                             f"{da[max(i, j)] + size[max(i, j)]:#x}) overlaps entry {min(i, j)}'s")
+    s0 = src.data_ptr()
+    for i in live.tolist():
+        if da[i] < s0 + src_n and s0 < da[i] + size[i]:
+            raise ValueError(f"{what}entry {i}: output [{da[i]:#x}, {da[i] + size[i]:#x}) overlaps the source")
+    return table, sizes
+
+
+def scatter_soa(table: np.ndarray, size: np.ndarray) -> np.ndarray:
+    """The [6][n] block K15 reads: a validated SCATTER_DTYPE table sorted by dst_addr, its fields row
+    by row, and the block-prefix row (ZG_SCATTER_BLK_END) that is the kernel's search key."""
+    order = np.argsort(table["dst_addr"], kind="stable")
+    table, size = table[order], size[order]
+    soa = np.empty((len(SCATTER_DTYPE.names) + 1, len(table)), dtype=np.uint64)
+    for k, f in enumerate(SCATTER_DTYPE.names):
+        soa[k] = table[f]
+    # aligned 16-byte destination blocks per entry: floor(dst / 16) .. ceil((dst + size) / 16); the
+    # end is formed from the last byte so that an output ending at 2^64 - 1 does not wrap
+    da = table["dst_addr"]
+    last = da + np.maximum(size, np.uint64(1)) - np.uint64(1)
+    blocks = np.where(size > 0, (last >> np.uint64(4)) - (da >> np.uint64(4)) + np.uint64(1), np.uint64(0))
+    soa[5] = np.cumsum(blocks, dtype=np.uint64)
+    return soa
+
+
+def slice_scatter(src: torch.Tensor, table, buffers, stream=None) -> None:
+    """Copy the kept slices of many tensors out of `src` (uint8, e.g. a verified safetensors file) to
+    absolute addresses in memory the caller owns: K15, csrc/gpu/scatter.hip.  :func:`slice_gather`
+    with the destination anywhere instead of in one arena.
+
+    table: SCATTER_DTYPE records, in any order.  Entry i is n_runs runs of run_bytes bytes, run r read
+    at src_off + r * src_stride, laid end to end at the address dst_addr (any alignment).  buffers: the
+    tensors that vouch for the destination memory, on src's device (the convention of
+    :func:`hash_chunks_at`).  Nothing can be checked on the device against absolute addresses, so a table
+    is refused here (ValueError naming the entry, before any launch) unless every run lies inside src,
+    every output lies inside the logical range of one tensor of `buffers`, the outputs are pairwise
+    disjoint and disjoint from src, and there are at most 2^32 - 1 entries.  Zero-size entries are
+    legal; empty and all-zero tables launch nothing.  Only output bytes are written, and no
+    destination byte is read: whatever surrounds an output keeps its value, down to the byte.  GPU
+    tensors: the table is sorted by dst_addr and uploaded with its block-prefix row as one block, then
+    one asynchronous launch on `stream` (default: the current stream); CPU tensors (host addresses): a
+    NumPy path with the same contract."""
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("slice_scatter: src must be a contiguous uint8 tensor")
+    buffers = list(buffers)
+    for k, t in enumerate(buffers):
+        if t.device != src.device:
+            raise ValueError(f"slice_scatter: buffer {k} is on {t.device}, src on {src.device}")
+    table, size = _check_scatter_table(table, src, buffers)
+    n = len(table)
+    if n == 0 or not size.any():
+        return
+    if src.device.type != "cuda":
+        return _slice_scatter_cpu(src.reshape(-1).numpy(), table)
+    H = hip()
+    soa = scatter_soa(table, size)
+    if stream is None:
+        st = _stream(src.device)
+        tab = _dev_array(soa, src.device)
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the table's upload and its free are ordered on the launch's stream
+            tab = _dev_array(soa, src.device)
+    assert soa.shape[0] == H.SCATTER_ROWS, "ZG_SCATTER_ROWS drift"
+    H.slice_scatter(src.data_ptr(), tab.data_ptr(), n, int(soa[5, -1]), st)
+
+
+def _slice_scatter_cpu(src: np.ndarray, table: np.ndarray) -> None:
+    import ctypes
+
+    for e in table:
+        so, rb, st, nr, da = (int(e[f]) for f in SCATTER_DTYPE.names)
+        if rb == 0 or nr == 0:
+            continue
+        out = np.frombuffer((ctypes.c_ubyte * (rb * nr)).from_address(da), dtype=np.uint8)  # the caller's memory
+        if nr == 1 or st == rb:
+            out[:] = src[so:so + rb * nr]
+            continue
+        runs = np.lib.stride_tricks.as_strided(src[so:], shape=(nr, rb), strides=(st, 1), writeable=False)
+        out.reshape(nr, rb)[...] = runs
+
+
+# ----------------------------------------------------------------------------------------------
 # K12: copy + re-hash chunks that are resident on the device under another revision
 # ----------------------------------------------------------------------------------------------
-REUSE_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u4"), ("index", "<u4")])
+REUSE_DTYPE =np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u4"), ("index", "<u4")])
 MAX_CHUNK = 128 * 1024
 
 

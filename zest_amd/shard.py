@@ -166,6 +166,38 @@ def _prod(xs) -> int:
     return n
 
 
+def tensor_runs(name: str, ent: dict, data_start: int, shard: Shard, file_size: int | None = None):
+    """The runs `shard` keeps of one safetensors header entry: (sliced shape, src_off, run_bytes,
+    src_stride, n_runs, nbytes) with src_off counted from the start of the file, or None when the
+    plan drops the tensor.  The entry is checked first (dtype, data_offsets against shape and
+    file_size).  Shared by `plan_file` (arena destinations) and `zest_amd.into` (the caller's)."""
+    isz = _itemsize(name, ent["dtype"])
+    shape = tuple(int(x) for x in ent["shape"])
+    a, b = (int(x) for x in ent["data_offsets"])
+    if any(x < 0 for x in shape) or a < 0 or b - a != _prod(shape) * isz:
+        raise ValueError(f"{name}: data_offsets [{a}, {b}) do not match shape {list(shape)} of {ent['dtype']}")
+    if file_size is not None and data_start + b > file_size:
+        raise ValueError(f"{name}: data_offsets [{a}, {b}) reach past the file ({file_size} bytes)")
+    act = shard.resolve(name, shape, ent["dtype"])
+    if act == "drop":
+        return None
+    if act is None:
+        out_shape, src_off, run, stride, n_runs = shape, data_start + a, b - a, b - a, 1
+    else:
+        dim, start, stop = act
+        inner = _prod(shape[dim + 1:]) * isz
+        out_shape = shape[:dim] + (stop - start,) + shape[dim + 1:]
+        src_off = data_start + a + start * inner
+        run, stride, n_runs = (stop - start) * inner, shape[dim] * inner, _prod(shape[:dim])
+    nbytes = run * n_runs
+    if nbytes == 0:
+        run = stride = n_runs = 0
+        src_off = data_start + a
+    elif run == stride or n_runs == 1:  # the slice is contiguous in the file: one run
+        run, stride, n_runs = nbytes, nbytes, 1
+    return out_shape, src_off, run, stride, n_runs, nbytes
+
+
 def plan_file(data_start: int, meta: dict, shard: Shard, file_size: int | None = None) -> FilePlan:
     """The slice table and arena layout of one safetensors file for `shard`.
 
@@ -177,31 +209,11 @@ def plan_file(data_start: int, meta: dict, shard: Shard, file_size: int | None =
     for name, ent in meta.items():
         if name == "__metadata__":
             continue
-        isz = _itemsize(name, ent["dtype"])
-        shape = tuple(int(x) for x in ent["shape"])
-        a, b = (int(x) for x in ent["data_offsets"])
-        if any(x < 0 for x in shape) or a < 0 or b - a != _prod(shape) * isz:
-            raise ValueError(f"{name}: data_offsets [{a}, {b}) do not match shape {list(shape)} of {ent['dtype']}")
-        if file_size is not None and data_start + b > file_size:
-            raise ValueError(f"{name}: data_offsets [{a}, {b}) reach past the file ({file_size} bytes)")
-        act = shard.resolve(name, shape, ent["dtype"])
-        if act == "drop":
+        runs = tensor_runs(name, ent, data_start, shard, file_size)
+        if runs is None:
             dropped.append(name)
             continue
-        if act is None:
-            out_shape, src_off, run, stride, n_runs = shape, data_start + a, b - a, b - a, 1
-        else:
-            dim, start, stop = act
-            inner = _prod(shape[dim + 1:]) * isz
-            out_shape = shape[:dim] + (stop - start,) + shape[dim + 1:]
-            src_off = data_start + a + start * inner
-            run, stride, n_runs = (stop - start) * inner, shape[dim] * inner, _prod(shape[:dim])
-        nbytes = run * n_runs
-        if nbytes == 0:
-            run = stride = n_runs = 0
-            src_off = data_start + a
-        elif run == stride or n_runs == 1:  # the slice is contiguous in the file: one run
-            run, stride, n_runs = nbytes, nbytes, 1
+        out_shape, src_off, run, stride, n_runs, nbytes = runs
         rows.append((src_off, run, stride, n_runs, pos))
         tensors.append(PlannedTensor(name, ent["dtype"], out_shape, pos, nbytes))
         pos = -(-(pos + nbytes) // ARENA_ALIGN) * ARENA_ALIGN
