@@ -339,6 +339,15 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("src"), py::arg("table"), py::arg("n"), py::arg("total_blocks"), py::arg("stream"),
      "K15: table is a device block of SCATTER_ROWS rows of n uint64 (src_off, run_bytes, src_stride, n_runs, "
      "dst_addr, blk_end), pre-validated by the caller (zest_amd.ops.slice_scatter)");
+  m.attr("CAST_ROWS") = int(ZG_CAST_ROWS);
+  m.attr("CAST_KINDS") = int(ZG_CAST_KINDS);
+  m.def("slice_scatter_cast", [](uintptr_t src, uintptr_t table, uint32_t n, uint64_t total_blocks, uintptr_t st) {
+    check(zg_slice_scatter_cast(P<const uint8_t>(src), P<const uint64_t>(table), n, total_blocks, S(st)),
+          "zg_slice_scatter_cast");
+  }, py::arg("src"), py::arg("table"), py::arg("n"), py::arg("total_blocks"), py::arg("stream"),
+     "K16: table is a device block of CAST_ROWS rows of n uint64 (src_off, run_bytes, src_stride, n_runs, "
+     "dst_addr, kind, blk_end over the converted sizes), pre-validated by the caller "
+     "(zest_amd.ops.slice_scatter_cast)");
   m.attr("SLICE_PEER_ROWS") = int(ZG_SLICE_PEER_ROWS);
   m.attr("MAX_SLICE_SRCS") = int(kZgMaxPeerSegs);
   m.def("slice_gather_peers", [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& lo,

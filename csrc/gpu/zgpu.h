@@ -219,6 +219,37 @@ enum {
 hipError_t zg_slice_scatter(const uint8_t* src, const uint64_t* table, uint32_t n, uint64_t total_blocks,
                             hipStream_t stream);
 
+// K16 (scatter_cast.hip): K15 with a float conversion on the way.  table: device block of
+// ZG_CAST_ROWS rows of n uint64 each: K15's five fields, kind[i] (one of ZG_CAST_F32_BF16 ..
+// ZG_CAST_F16_BF16), then blk_end.  run_bytes, src_off and src_stride count SOURCE bytes; entry i
+// writes size = n_runs * run_bytes / src_item * dst_item bytes at dst_addr[i], and blk_end is K15's
+// prefix sum over those output sizes.  dst_addr[i] is a multiple of the destination item, run_bytes[i]
+// of the source item; src_off and src_stride are arbitrary (a source element may sit at any byte
+// address).  Round to nearest even, one rounding, overflow to infinity, subnormals and signed zeros
+// kept, NaN stays NaN (sign and payload unspecified).  Stores as K15, with 2- or 4-byte element stores
+// for its byte stores; no destination byte is read.  The caller vouches for the table.
+enum {
+  ZG_CAST_SRC_OFF = 0,
+  ZG_CAST_RUN_BYTES = 1,
+  ZG_CAST_SRC_STRIDE = 2,
+  ZG_CAST_N_RUNS = 3,
+  ZG_CAST_DST_ADDR = 4,
+  ZG_CAST_KIND = 5,
+  ZG_CAST_BLK_END = 6,
+  ZG_CAST_ROWS = 7
+};
+enum {
+  ZG_CAST_F32_BF16 = 0,
+  ZG_CAST_F32_F16 = 1,
+  ZG_CAST_BF16_F32 = 2,
+  ZG_CAST_F16_F32 = 3,
+  ZG_CAST_BF16_F16 = 4,
+  ZG_CAST_F16_BF16 = 5,
+  ZG_CAST_KINDS = 6
+};
+hipError_t zg_slice_scatter_cast(const uint8_t* src, const uint64_t* table, uint32_t n, uint64_t total_blocks,
+                                 hipStream_t stream);
+
 // K8: pull each segment's bytes from a peer's IPC-mapped arena (xGMI) into this GPU's arena;
 // every segment is read concurrently.  src[i] and dst[i] must be congruent mod 16.
 enum { kZgMaxPeerSegs = 16 };

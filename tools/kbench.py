@@ -632,6 +632,86 @@ def main():
             del out, dests, tab10_d, tab15_d, srcs, got
         del views
 
+    if want("slice_scatter_cast"):
+        # K16 slice_scatter_cast on K15's set-up (the second Llama-3.1-70B shard's table, rank 0 of 8, then
+        # world 1; every destination a separately allocated tensor), the file's bytes read as F32 into
+        # bf16 destinations and as BF16 into f32 ones, next to the per-tensor dst.copy_(file_view) loop
+        # (torch's converting copy, what pull() + copy_ runs) and to K15 of as many source bytes, the
+        # copy floor.  The expectation to test: K16 is no slower than the copy_ loop, which moves the same
+        # bytes with one launch per tensor.  Rows alternate, one timed launch per row and iteration;
+        # median and range per row.
+        from zest_amd import device as zdev
+        from zest_amd import models
+        from zest_amd.shard import Shard, plan_file
+
+        sf = models.get("llama-3.1-70b").shards()[1]
+        start, meta = zdev.parse_safetensors_header(sf.header)
+        fbuf = arena if n >= sf.size else ops.padded_empty(sf.size, dev)
+        if fbuf is not arena:
+            ops.fill_synthetic(fbuf, 2, 0, 0)
+        fbuf = fbuf[:sf.size]
+        for world in (8, 1):
+            plan = plan_file(start, meta, Shard(0, world), sf.size)
+            tb = {f: plan.table[f].astype(np.int64) for f in ops.SCATTER_DTYPE.names[:4]}
+            live = np.flatnonzero(tb["run_bytes"] * tb["n_runs"])
+            assert not ((tb["src_off"] | tb["run_bytes"] | tb["src_stride"])[live] % 4).any()  # whole F32 items
+            flat = [ops.padded_empty(int(tb["run_bytes"][i] * tb["n_runs"][i]), dev) for i in live]  # K15's destinations
+            t15 = np.empty(len(live), dtype=ops.SCATTER_DTYPE)
+            for f in tb:
+                t15[f] = tb[f][live]
+            t15["dst_addr"] = [d.data_ptr() for d in flat]
+            soa15 = ops.scatter_soa(t15, t15["run_bytes"] * t15["n_runs"])
+            soa15_d = torch.from_numpy(soa15.view(np.int64)).to(dev)
+            for s_name, d_name, sdt, ddt in (("F32", "BF16", torch.float32, torch.bfloat16),
+                                             ("BF16", "F32", torch.bfloat16, torch.float32)):
+                si = sdt.itemsize
+                whole = fbuf[:sf.size // si * si].view(sdt)
+                srcs = [torch.as_strided(whole, (int(tb["n_runs"][i]), int(tb["run_bytes"][i]) // si),
+                                         (int(tb["src_stride"][i]) // si, 1), int(tb["src_off"][i]) // si) for i in live]
+                dests = [torch.empty(s_.shape, dtype=ddt, device=dev) for s_ in srcs]
+                t16 = np.empty(len(live), dtype=ops.CAST_DTYPE)
+                for f in tb:
+                    t16[f] = tb[f][live]
+                t16["dst_addr"] = [d.data_ptr() for d in dests]
+                t16["kind"] = ops.CAST_KINDS[(s_name, d_name)]
+                src_bytes = int((t16["run_bytes"] * t16["n_runs"]).sum())
+                out_bytes = src_bytes // si * ddt.itemsize
+                soa16 = ops.scatter_cast_soa(t16, t16["run_bytes"] * t16["n_runs"] // np.uint64(si) * np.uint64(ddt.itemsize))
+                soa16_d = torch.from_numpy(soa16.view(np.int64)).to(dev)
+
+                def copy_loop():
+                    for d, s_ in zip(dests, srcs):
+                        d.copy_(s_)
+
+                rows = (("slice_scatter_cast[kernel]", lambda: H.slice_scatter_cast(
+                            fbuf.data_ptr(), soa16_d.data_ptr(), soa16.shape[1], int(soa16[-1, -1]), st)),
+                        ("slice_scatter_cast[ops]", lambda: ops.slice_scatter_cast(fbuf, t16, dests)),
+                        ("dst_copy_convert_loop", copy_loop),
+                        ("slice_scatter[kernel, same source bytes]", lambda: H.slice_scatter(
+                            fbuf.data_ptr(), soa15_d.data_ptr(), soa15.shape[1], int(soa15[-1, -1]), st)))
+                ms = {name: [] for name, _ in rows}
+                for _ in range(max(7, a.iters)):
+                    for name, fn in rows:
+                        ms[name].append(timed(fn, 1))
+                med = {name: float(np.median(v)) for name, v in ms.items()}
+                for name, v in ms.items():
+                    moved = 2 * src_bytes if name.startswith("slice_scatter[") else src_bytes + out_bytes
+                    emit(kernel=name, cast=f"{s_name}->{d_name}", world=world, src_bytes=src_bytes, out_bytes=out_bytes,
+                         ms=med[name], ms_min=min(v), ms_max=max(v), iters=len(v), moved_gbps=moved / med[name] / 1e6,
+                         tensors=len(live), k16_over_k15=med["slice_scatter_cast[kernel]"] / med[rows[3][0]],
+                         k16_over_copy_loop=med["slice_scatter_cast[kernel]"] / med["dst_copy_convert_loop"])
+                copy_loop()
+                ref = [d.clone() for d in dests]
+                for d in dests:
+                    d.zero_()
+                rows[0][1]()  # the kernel row alone refills the destinations: compare with torch's converts off NaN
+                for d, r, s_ in zip(dests, ref, srcs):
+                    ok = torch.isnan(s_) | (d.view(torch.int16 if ddt.itemsize == 2 else torch.int32)
+                                            == r.view(torch.int16 if ddt.itemsize == 2 else torch.int32))
+                    assert bool(ok.all()) and bool(torch.isnan(d)[torch.isnan(s_)].all())
+                del dests, srcs, soa16_d, ref
+            del flat, soa15_d
+
     if want("reuse_chunks"):
         # K12 reuse_chunks: 1 GiB of CDC-sized chunks (the size mix of 64 MiB of the arena's own bytes,
         # repeated) at random source and destination misalignments, next to the two passes it fuses, built

@@ -58,7 +58,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
          group=None, repo_type: str = "model", verbose: bool = False, direct: bool | None = None,
          save_snapshot: bool = False, threads: int = 16, staging_bytes: int = 1 << 30, stats: dict | None = None,
          exchange: str = "auto", round_bytes: int | None = None, seed=False, shard=None,
-         scratch_bytes: int | None = None, base=None, into=None, strict: bool = True):
+         scratch_bytes: int | None = None, base=None, into=None, strict: bool = True, cast: bool = False):
     """Download `repo@revision` via zest.
 
     * default: returns the HF-cache snapshot directory (reference behaviour).
@@ -132,7 +132,20 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       receives file_bytes, written_bytes, tensors, skipped_files, missing, groups, scratch_bytes and
       scatter_s.  Refused with device="all", base=, seed=, save_snapshot=True, direct=False and no
       device.
+    * cast=True, with into= only: a wanted tensor stored in another float dtype than its destination's
+      is converted on the way, F32, F16 and BF16 to each other (round to nearest even, overflow to
+      infinity, subnormals kept, NaN stays NaN).  Files are verified in their stored dtype; per
+      verified file the tensors whose dtype matches go through ops.slice_scatter as before and the
+      others through one ops.slice_scatter_cast launch (kernel K16), so peak device memory stays the
+      model plus one scratch, where pull() followed by a converting copy_ holds the whole checkpoint
+      next to the model.  Any other dtype pair (integers, bool, F8, F64) is still refused with a
+      ValueError naming the tensor, before anything of that file is written.  `stats["into"]` also
+      receives cast_tensors and cast_bytes_in (stored bytes converted); written_bytes counts
+      destination bytes.  cast=False (default) converts nothing.  Refused without into=.
     """
+    if cast and into is None:
+        raise ValueError("cast=True needs into=: the conversion is to the dtype of destinations the caller owns; a "
+                         "plain pull returns the tensors in the checkpoint's dtype")
     if into is not None:
         if device is None:
             raise ValueError("into= needs a device: use device='cuda:N' (or 'cpu'), the device the destinations are "
@@ -225,7 +238,7 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
                               threads=threads, staging_bytes=staging_bytes, include=include, seed=seed, shard=shard,
                               scratch_bytes=scratch_bytes,
                               stats=stats if shard is not None or base is not None or into is not None else None,
-                              base=base, into=into, strict=strict)
+                              base=base, into=into, strict=strict, cast=cast)
     from .device import load_snapshot
 
     res = _client.pull_detailed(repo, revision, **kw)

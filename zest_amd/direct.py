@@ -34,6 +34,8 @@ gather_s.
 `into=` (a {checkpoint tensor name: destination tensor} dict or a torch.nn.Module): the same flow,
 but after a group of files verifies `ops.slice_scatter` copies the wanted tensors to the addresses
 of tensors the caller already owns, so nothing but the scratch is allocated (zest_amd.into).
+`cast=True` with it: tensors stored in another float dtype than their destination's (F32, F16, BF16)
+are converted on the way by `ops.slice_scatter_cast`.
 """
 from __future__ import annotations
 
@@ -51,7 +53,10 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
                    tracker=None, dht: bool = True, dht_bootstrap=None, repo_type: str = "model",
                    save_snapshot: bool = False, staging_bytes: int = 1 << 30, threads: int = 16, include=None, seed=False,
                    shard=None, scratch_bytes: int | None = None, stats: dict | None = None, base=None, into=None,
-                   strict: bool = True):
+                   strict: bool = True, cast: bool = False):
+    if cast and into is None:
+        raise ValueError("cast=True needs into=: the conversion is to the dtype of destinations the caller owns; a "
+                         "plain pull returns the tensors in the checkpoint's dtype")
     if into is not None:
         if device is None:
             raise ValueError("into= needs a device: use device='cuda:N' (or 'cpu'), the device the destinations are on")
@@ -98,7 +103,7 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
 
         return pull_into(repo, revision, dev, into, None if shard is None else zshard.as_shard(shard), scratch_bytes,
                          stats, strict, p2p=p2p, peers=peers, tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap,
-                         repo_type=repo_type, staging_bytes=staging_bytes, threads=threads, include=include)
+                         repo_type=repo_type, staging_bytes=staging_bytes, threads=threads, include=include, cast=cast)
     if shard is not None:
         return _pull_sharded(repo, revision, dev, zshard.as_shard(shard), scratch_bytes, stats, p2p=p2p, peers=peers,
                              tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap, repo_type=repo_type,

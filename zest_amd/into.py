@@ -14,14 +14,26 @@ group, through one reused scratch; after a group verifies, one `ops.slice_scatte
 to the destinations' addresses.  Peak device memory is the model plus one scratch, where
 `pull()` followed by `param.copy_()` holds two models.
 
+    model = build_model().to("cuda:0", torch.bfloat16)       # served in bf16, the checkpoint is F32
+    zest_amd.pull(repo, device="cuda:0", into=model, cast=True)
+
+`cast=True`: a wanted tensor stored in another float dtype than its destination's is converted on the
+way, F32 / F16 / BF16 to each other, round to nearest even.  The file is still verified in its stored
+dtype (the Xet hash is over the stored bytes); the conversion is in the scatter: per verified file the
+tensors whose dtype matches go through `ops.slice_scatter` untouched and the others through one
+`ops.slice_scatter_cast` launch (K16, csrc/gpu/scatter_cast.hip), at most two launches per file, all
+planning and every refusal before the first.  Peak device memory stays the model plus one scratch,
+where `pull()` followed by a converting `param.copy_()` holds the whole checkpoint next to the model.
+
 No byte of a file reaches a destination before that whole file has passed its Xet hash, and a file
 whose tensors do not fit their destinations (dtype, sliced shape) writes nothing: a file that fails
 leaves its destinations untouched, files before it stay written.  The bytes are written behind
 autograd's back (version counters are not bumped), and nothing may run the model during the call.
 
 Limits: one process (no collective form), no delta (`base=` is refused: every wanted file is
-fetched), network bytes are those of a sharded pull, destinations must be contiguous, no dtype
-conversion.
+fetched), network bytes are those of a sharded pull, destinations must be contiguous, dtype
+conversion only with `cast=True` and only among F32, F16 and BF16 (no F8, F64 or integer conversions,
+no scaling).
 """
 from __future__ import annotations
 
@@ -95,10 +107,16 @@ class Target:
         return zshard.Shard(0, 1, plan) if sh is None else zshard.Shard(sh.rank, sh.world, plan)
 
 
-def plan_file_into(data_start: int, meta: dict, wsh, dests: dict, file_size: int | None = None):
+SAME = (1 << 64) - 1  # `kind` of a tensor that needs no conversion in a cast=True plan
+
+
+def plan_file_into(data_start: int, meta: dict, wsh, dests: dict, file_size: int | None = None, cast: bool = False):
     """The scatter table of one safetensors file: (ops.SCATTER_DTYPE table, names, bytes written).
     wsh: `Target.shard(...)`.  Raises ValueError naming the tensor when a wanted tensor's dtype or
-    (sliced) shape differs from its destination's; the run arithmetic is `shard.tensor_runs`."""
+    (sliced) shape differs from its destination's; the run arithmetic is `shard.tensor_runs`.
+    cast=True: the table is ops.CAST_DTYPE, its runs in stored (source) bytes; `kind` is the
+    ops.CAST_KINDS code of a tensor whose dtype differs from its destination's and SAME for the
+    others, and only pairs outside ops.CAST_KINDS are refused.  Bytes written are destination bytes."""
     rows, names, total = [], [], 0
     for name, ent in meta.items():
         if name == "__metadata__":
@@ -108,28 +126,49 @@ def plan_file_into(data_start: int, meta: dict, wsh, dests: dict, file_size: int
             continue
         out_shape, src_off, run, stride, n_runs, nbytes = runs
         t = dests[name]
+        kind = SAME
         if zdev.ST_DTYPES[ent["dtype"]] != t.dtype:
-            raise ValueError(f"{name}: the checkpoint holds {ent['dtype']}, the destination is {t.dtype} "
-                             "(into= converts nothing)")
+            if not cast:
+                raise ValueError(f"{name}: the checkpoint holds {ent['dtype']}, the destination is {t.dtype} "
+                                 "(into= converts nothing)")
+            kind = ops.CAST_KINDS.get((ent["dtype"], _ST_NAMES[t.dtype]))
+            if kind is None:
+                raise ValueError(f"{name}: the checkpoint holds {ent['dtype']}, the destination is {t.dtype} "
+                                 "(cast=True converts F32, F16 and BF16 to each other, nothing else)")
         if tuple(out_shape) != tuple(t.shape):
             raise ValueError(f"{name}: the checkpoint gives shape {list(out_shape)}, the destination has "
                              f"{list(t.shape)}")
-        rows.append((src_off, run, stride, n_runs, t.data_ptr()))
+        rows.append((src_off, run, stride, n_runs, t.data_ptr(), kind) if cast
+                    else (src_off, run, stride, n_runs, t.data_ptr()))
         names.append(name)
-        total += nbytes
-    return np.array(rows, dtype=ops.SCATTER_DTYPE), names, total
+        total += nbytes if kind == SAME else _nbytes(t)
+    return np.array(rows, dtype=ops.CAST_DTYPE if cast else ops.SCATTER_DTYPE), names, total
 
 
-def _scatter_file(buf: torch.Tensor, path: str, wsh, target: Target, written: dict, info: dict) -> None:
-    """Plan one verified file in `buf`, check it against the destinations and scatter it: one launch.
-    Everything that can refuse the file runs before the launch."""
+def _scatter_file(buf: torch.Tensor, path: str, wsh, target: Target, written: dict, info: dict,
+                  cast: bool = False) -> None:
+    """Plan one verified file in `buf`, check it against the destinations and scatter it: one launch,
+    with cast=True one for the tensors copied as they are and one for the converted ones.  Everything
+    that can refuse the file runs before the first launch."""
     (hlen,) = struct.unpack("<Q", buf[:8].cpu().numpy().tobytes())
     start, meta = zdev.parse_safetensors_header(buf[:8 + hlen].cpu().numpy().tobytes())
-    table, names, total = plan_file_into(start, meta, wsh, target.dests, buf.numel())
+    table, names, total = plan_file_into(start, meta, wsh, target.dests, buf.numel(), cast)
     for name in names:
         if name in written:
             raise ValueError(f"duplicate tensor {name} in {path}")
-    ops.slice_scatter(buf, table, [target.dests[n] for n in names])
+    bufs = [target.dests[n] for n in names]
+    if cast:
+        conv = table[table["kind"] != SAME]
+        same = np.empty(len(table) - len(conv), dtype=ops.SCATTER_DTYPE)
+        for f in ops.SCATTER_DTYPE.names:
+            same[f] = table[f][table["kind"] == SAME]
+        ops.check_scatter_cast(buf, conv, bufs)  # slice_scatter_cast itself would refuse only after the first launch
+        ops.slice_scatter(buf, same, bufs)
+        ops.slice_scatter_cast(buf, conv, bufs)
+        info["cast_tensors"] += len(conv)
+        info["cast_bytes_in"] += int((conv["run_bytes"] * conv["n_runs"]).sum())
+    else:
+        ops.slice_scatter(buf, table, bufs)
     for name in names:
         written[name] = target.dests[name]
     info["file_bytes"] += buf.numel()
@@ -138,7 +177,7 @@ def _scatter_file(buf: torch.Tensor, path: str, wsh, target: Target, written: di
 
 
 def pull_into(repo, revision, dev, into, sh, scratch_bytes, stats, strict, *, p2p, peers, tracker, dht, dht_bootstrap,
-              repo_type, staging_bytes, threads, include):
+              repo_type, staging_bytes, threads, include, cast=False):
     """pull_to_device(into=...): see the module docstring.  Returns {name: destination} of what was
     written, after the device has finished the scatters."""
     target = Target(into, dev)  # refusals first: nothing is listed or fetched for a target that cannot be filled
@@ -160,7 +199,7 @@ def pull_into(repo, revision, dev, into, sh, scratch_bytes, stats, strict, *, p2
     cuda = dev.type == "cuda"
     written: dict[str, torch.Tensor] = {}
     info = {"file_bytes": 0, "written_bytes": 0, "tensors": 0, "skipped_files": sorted(skipped), "missing": [],
-            "groups": 0, "scratch_bytes": 0, "scatter_s": 0.0}
+            "groups": 0, "scratch_bytes": 0, "scatter_s": 0.0, "cast_tensors": 0, "cast_bytes_in": 0}
     if stats is not None:
         stats["into"] = info  # also what a pull that raises half way leaves behind
     timed = []  # cuda: (start, end) events around each group's scatters, read once at the end
@@ -183,7 +222,7 @@ def pull_into(repo, revision, dev, into, sh, scratch_bytes, stats, strict, *, p2
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record()
                     for f, o in g:
-                        _scatter_file(scratch[o:o + f["size"]], f["path"], wsh, target, written, info)
+                        _scatter_file(scratch[o:o + f["size"]], f["path"], wsh, target, written, info, cast)
                     ev1.record()
                     timed.append((ev0, ev1))
                     dp.order_after(ev1.cuda_event)  # the next group overwrites the scratch these scatters read
@@ -195,7 +234,7 @@ def pull_into(repo, revision, dev, into, sh, scratch_bytes, stats, strict, *, p2
                 hf.fetch_files([(f["xet_hash"], scratch.data_ptr() + o, f["size"]) for f, o in g])
                 t0 = time.perf_counter()
                 for f, o in g:
-                    _scatter_file(scratch[o:o + f["size"]], f["path"], wsh, target, written, info)
+                    _scatter_file(scratch[o:o + f["size"]], f["path"], wsh, target, written, info, cast)
                 info["scatter_s"] += time.perf_counter() - t0
     if plain:  # non-Xet safetensors: the host route, then the same plan and scatter, file by file
         r = _core.pull(repo, revision, *net, [f["path"] for f in plain], True, 0, repo_type)
@@ -204,10 +243,10 @@ def pull_into(repo, revision, dev, into, sh, scratch_bytes, stats, strict, *, p2
             t0 = time.perf_counter()
             if cuda:
                 with torch.cuda.device(dev):
-                    _scatter_file(buf, f["path"], wsh, target, written, info)
+                    _scatter_file(buf, f["path"], wsh, target, written, info, cast)
                     torch.cuda.current_stream(dev).synchronize()  # buf is freed before the next file loads
             else:
-                _scatter_file(buf, f["path"], wsh, target, written, info)
+                _scatter_file(buf, f["path"], wsh, target, written, info, cast)
             info["scatter_s"] += time.perf_counter() - t0
             del buf
     if cuda:

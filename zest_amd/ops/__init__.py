@@ -7,7 +7,7 @@ CPU tensors take the C++ host oracle in zest_amd._core, which is what the gloo/C
 
 Kernel map: K1 hash_ranges/hash_placed, K2 merkle_roots, K3+K4 ingest_terms,
 K5 cdc_candidates, K7 pack_chunks, K9 serve_pack, K10 slice_gather, K11 slice_gather_peers,
-K12 reuse_chunks, K13 dedup_chunks, K15 slice_scatter.
+K12 reuse_chunks, K13 dedup_chunks, K15 slice_scatter, K16 slice_scatter_cast.
 """
 from __future__ import annotations
 
@@ -781,17 +781,30 @@ SCATTER_DTYPE = np.dtype([("src_off", "<u8"), ("run_bytes", "<u8"), ("src_stride
 MAX_SCATTER_ENTRIES = (1 << 32) - 1
 
 
-def _check_scatter_table(table, src: torch.Tensor, buffers) -> tuple[np.ndarray, np.ndarray]:
+def _check_scatter_table(table, src: torch.Tensor, buffers, cast: bool = False) -> tuple[np.ndarray, np.ndarray]:
     """Validate a scatter table against its source and the buffers that vouch for the destinations;
-    returns (table, output bytes per entry).  Every message names the entry by its index in `table`."""
-    what = "slice_scatter: "
+    returns (table, output bytes per entry).  Every message names the entry by its index in `table`.
+    cast: a CAST_DTYPE table (K16); its kinds and item multiples are checked first, and everything on
+    the destination side is computed on the converted sizes."""
+    what = "slice_scatter_cast: " if cast else "slice_scatter: "
     n = table.size if isinstance(table, np.ndarray) else len(table)
     if n > MAX_SCATTER_ENTRIES:  # before anything is copied: the kernel indexes entries with 32 bits
         raise ValueError(f"{what}{n} entries, at most {MAX_SCATTER_ENTRIES}")
-    table = np.ascontiguousarray(table, dtype=SCATTER_DTYPE).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=CAST_DTYPE if cast else SCATTER_DTYPE).reshape(-1)
     so, rb, st, nr, da = ([int(x) for x in table[f]] for f in SCATTER_DTYPE.names)  # Python ints: no wrap-around
     src_n = src.numel()
     size = [rb[i] * nr[i] for i in range(len(table))]
+    if cast:
+        for i, kind in enumerate(int(x) for x in table["kind"]):
+            if kind not in _CAST_ITEMS:
+                raise ValueError(f"{what}entry {i}: unknown kind {kind} (ops.CAST_KINDS)")
+            si, di = _CAST_ITEMS[kind]
+            if rb[i] % si:
+                raise ValueError(f"{what}entry {i}: run_bytes {rb[i]} is no multiple of the source item ({si} bytes)")
+            size[i] = size[i] // si * di
+            if size[i] and da[i] % di:
+                raise ValueError(f"{what}entry {i}: dst_addr {da[i]:#x} is no multiple of the destination item "
+                                 f"({di} bytes)")
     for i, n in enumerate(size):
         if n and st[i] < rb[i]:
             raise ValueError(f"{what}entry {i}: src_stride {st[i]} < run_bytes {rb[i]}")
@@ -820,17 +833,21 @@ def _check_scatter_table(table, src: torch.Tensor, buffers) -> tuple[np.ndarray,
 def scatter_soa(table: np.ndarray, size: np.ndarray) -> np.ndarray:
     """The [6][n] block K15 reads: a validated SCATTER_DTYPE table sorted by dst_addr, its fields row
     by row, and the block-prefix row (ZG_SCATTER_BLK_END) that is the kernel's search key."""
+    return _scatter_soa(table, size, SCATTER_DTYPE)
+
+
+def _scatter_soa(table: np.ndarray, size: np.ndarray, dtype: np.dtype) -> np.ndarray:
     order = np.argsort(table["dst_addr"], kind="stable")
     table, size = table[order], size[order]
-    soa = np.empty((len(SCATTER_DTYPE.names) + 1, len(table)), dtype=np.uint64)
-    for k, f in enumerate(SCATTER_DTYPE.names):
+    soa = np.empty((len(dtype.names) + 1, len(table)), dtype=np.uint64)
+    for k, f in enumerate(dtype.names):
         soa[k] = table[f]
     # aligned 16-byte destination blocks per entry: floor(dst / 16) .. ceil((dst + size) / 16); the
     # end is formed from the last byte so that an output ending at 2^64 - 1 does not wrap
     da = table["dst_addr"]
     last = da + np.maximum(size, np.uint64(1)) - np.uint64(1)
     blocks = np.where(size > 0, (last >> np.uint64(4)) - (da >> np.uint64(4)) + np.uint64(1), np.uint64(0))
-    soa[5] = np.cumsum(blocks, dtype=np.uint64)
+    soa[-1] = np.cumsum(blocks, dtype=np.uint64)
     return soa
 
 
@@ -889,6 +906,86 @@ def _slice_scatter_cpu(src: np.ndarray, table: np.ndarray) -> None:
             continue
         runs = np.lib.stride_tricks.as_strided(src[so:], shape=(nr, rb), strides=(st, 1), writeable=False)
         out.reshape(nr, rb)[...] = runs
+
+
+# ----------------------------------------------------------------------------------------------
+# K16: K15 with a float conversion on the way (a checkpoint's dtype -> the destinations' dtype)
+# ----------------------------------------------------------------------------------------------
+CAST_DTYPE = np.dtype(SCATTER_DTYPE.descr + [("kind", "<u8")])
+# (stored dtype, destination dtype) by safetensors name -> ZG_CAST_* code
+CAST_KINDS = {("F32", "BF16"): 0, ("F32", "F16"): 1, ("BF16", "F32"): 2, ("F16", "F32"): 3, ("BF16", "F16"): 4,
+              ("F16", "BF16"): 5}
+_CAST_TORCH = {"F32": torch.float32, "F16": torch.float16, "BF16": torch.bfloat16}
+_CAST_ITEMS = {code: (_CAST_TORCH[s].itemsize, _CAST_TORCH[d].itemsize) for (s, d), code in CAST_KINDS.items()}
+
+
+def scatter_cast_soa(table: np.ndarray, size: np.ndarray) -> np.ndarray:
+    """The [7][n] block K16 reads: a validated CAST_DTYPE table sorted by dst_addr, its fields row by
+    row (kind last), and the block-prefix row (ZG_CAST_BLK_END) over the converted sizes `size`."""
+    return _scatter_soa(table, size, CAST_DTYPE)
+
+
+def check_scatter_cast(src: torch.Tensor, table, buffers) -> tuple[np.ndarray, np.ndarray]:
+    """Every refusal of :func:`slice_scatter_cast` without the launch, for a caller that has other
+    launches to make first (zest_amd.into): returns (the CAST_DTYPE table, output bytes per entry)."""
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("slice_scatter_cast: src must be a contiguous uint8 tensor")
+    buffers = list(buffers)
+    for k, t in enumerate(buffers):
+        if t.device != src.device:
+            raise ValueError(f"slice_scatter_cast: buffer {k} is on {t.device}, src on {src.device}")
+    return _check_scatter_table(table, src, buffers, cast=True)
+
+
+def slice_scatter_cast(src: torch.Tensor, table, buffers, stream=None) -> None:
+    """:func:`slice_scatter` with a float conversion on the way: K16, csrc/gpu/scatter_cast.hip.  The
+    kept slices of tensors stored in one float dtype go out of `src` (uint8, a verified file in its
+    stored dtype) to destinations of another.
+
+    table: CAST_DTYPE records, in any order: slice_scatter's fields, counted in SOURCE bytes, and
+    `kind`, a CAST_KINDS code (F32, F16, BF16 to each other).  Entry i writes n_runs * run_bytes /
+    source item * destination item bytes at dst_addr.  Round to nearest even in one rounding, overflow
+    to infinity, subnormals and signed zeros kept; a NaN stays a NaN with unspecified sign and payload.
+    Refused (ValueError naming the entry, before any launch): everything slice_scatter refuses, with
+    the destination side computed on the converted sizes; an unknown kind; a run_bytes that is no
+    multiple of the source item; a dst_addr that is no multiple of the destination item.  src_off and
+    src_stride are arbitrary, so source elements may sit at any byte address.  Only output elements are
+    written and no destination byte is read.  Empty and all-zero tables launch nothing.  GPU tensors:
+    one sorted upload and one asynchronous launch on `stream`, as slice_scatter; CPU tensors (host
+    addresses): torch's own converts, entry by entry."""
+    table, size = check_scatter_cast(src, table, buffers)
+    n = len(table)
+    if n == 0 or not size.any():
+        return
+    if src.device.type != "cuda":
+        return _slice_scatter_cast_cpu(src.reshape(-1).numpy(), table)
+    H = hip()
+    soa = scatter_cast_soa(table, size)
+    if stream is None:
+        st = _stream(src.device)
+        tab = _dev_array(soa, src.device)
+    else:
+        st = stream.cuda_stream
+        with torch.cuda.stream(stream):  # the table's upload and its free are ordered on the launch's stream
+            tab = _dev_array(soa, src.device)
+    assert soa.shape[0] == H.CAST_ROWS and len(CAST_KINDS) == H.CAST_KINDS, "ZG_CAST_ROWS drift"
+    H.slice_scatter_cast(src.data_ptr(), tab.data_ptr(), n, int(soa[-1, -1]), st)
+
+
+def _slice_scatter_cast_cpu(src: np.ndarray, table: np.ndarray) -> None:
+    import ctypes
+
+    dtypes = {code: (_CAST_TORCH[s], _CAST_TORCH[d]) for (s, d), code in CAST_KINDS.items()}
+    for e in table:
+        so, rb, st, nr, da, kind = (int(e[f]) for f in CAST_DTYPE.names)
+        if rb == 0 or nr == 0:
+            continue
+        sdt, ddt = dtypes[kind]
+        runs = np.lib.stride_tricks.as_strided(src[so:], shape=(nr, rb), strides=(st, 1), writeable=False)
+        stored = torch.from_numpy(runs.copy().reshape(-1)).view(sdt)  # an aligned copy of the runs
+        conv = stored.to(ddt).view(torch.uint8).numpy()
+        out = np.frombuffer((ctypes.c_ubyte * len(conv)).from_address(da), dtype=np.uint8)  # the caller's memory
+        out[:] = conv
 
 
 # ----------------------------------------------------------------------------------------------
