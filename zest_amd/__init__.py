@@ -130,8 +130,21 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
       passed in} for every tensor written, after the device has finished.  Autograd version counters
       are not bumped, and the caller must not run the model during the call.  `stats["into"]`
       receives file_bytes, written_bytes, tensors, skipped_files, missing, groups, scratch_bytes and
-      scatter_s.  Refused with device="all", base=, seed=, save_snapshot=True, direct=False and no
-      device.
+      scatter_s.  Refused with device="all", seed=, save_snapshot=True, direct=False and no device.
+      The returned dict is a `zest_amd.into.Landed`: it also carries `.record`, plain data that says
+      which chunks the destinations hold.
+    * into=target with base= (the Landed of an earlier into= pull of the same destinations, or any
+      other base): the model is updated in place.  Terms whose chunks all lie in the base are hashed
+      where they lie (ops.hash_chunks_at), the others are fetched into a patch scratch; once the file's
+      Merkle root equals its Xet hash, chunks already at their place are kept, other resident chunks are
+      gathered and re-hashed (ops.reuse_chunks), and ops.slice_scatter writes only the fetched and the
+      moved pieces.  Peak memory above the model is the changed bytes plus small tables.  A file that
+      misses its hash (destinations modified since) wrote nothing and is pulled whole instead.  The
+      returned Landed carries the new record, so calls chain.  `stats["into"]["delta"]` receives
+      kept_terms, kept_bytes, moved_chunks, moved_bytes, fetched_terms, fetched_bytes, applied_bytes,
+      seam_chunks, seam_bytes, patch_bytes, fallback_files, fallback_bytes, check_s, fetch_s, apply_s,
+      bind_s (the part of check_s spent binding the record) and per-file counters under files.  Refused with shard= and cast=True.  A Landed is also a
+      plain base: pull(repo, rev, device=..., base=landed) copies out of the model's tensors.
     * cast=True, with into= only: a wanted tensor stored in another float dtype than its destination's
       is converted on the way, F32, F16 and BF16 to each other (round to nearest even, overflow to
       infinity, subnormals kept, NaN stays NaN).  Files are verified in their stored dtype; per
@@ -153,9 +166,9 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
         if device == "all":
             raise ValueError("into= is not supported with device='all' (swarm pulls): run one process per GPU with "
                              "device='cuda:N' and that GPU's own destinations")
-        if base is not None:
-            raise ValueError("into= is not supported with base=: nothing records yet which chunks the destinations "
-                             "hold; pull with base= into new tensors, or with into= without a base")
+        if base is not None and cast:
+            raise ValueError("base= is not supported with cast=True: converted destinations do not hold the stored "
+                             "bytes, so nothing of them can be verified or kept; pull with cast=True without a base")
         if seed is not False and seed is not None:
             raise ValueError("into= is not supported with seed=: the file bytes do not stay resident as files; seed "
                              "from a plain device pull")
@@ -178,6 +191,10 @@ def pull(repo: str, revision: str = "main", *, device=None, as_tensors: bool = F
         if direct is False:
             raise ValueError("base= is not supported with direct=False (the snapshot path): resident chunks are "
                              "copied into the buffers of a device-direct pull; leave direct at its default")
+        if into is not None:  # every refusal of a base before any request; a Landed is bound here, once
+            from .delta import as_resident_set
+
+            base = as_resident_set(base, device)
     if shard is not None:
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu'); a snapshot pull has no tensors "

@@ -18,8 +18,10 @@ file's Xet hash.  A file that misses with reused terms (the base tensors were mo
 exactly those terms fetched from the network and is checked again.
 
 Limits: granularity is the whole term (the CAS cuts terms at every changed chunk); the base must be
-on the pull's device (no peer reads); nothing is updated in place, so peak memory is old + new until
-the caller drops the base; a resident set does not outlive its process, so the CLI has no `--base`.
+on the pull's device (no peer reads); a plain delta pull writes new buffers, so peak memory is old + new
+until the caller drops the base (`pull(..., into=model, base=landed)`, zest_amd.into, is the form that
+updates a model's own tensors in place and writes only the changed chunks); a resident set does not
+outlive its process, so the CLI has no `--base`.
 """
 from __future__ import annotations
 
@@ -52,6 +54,8 @@ class ResidentSet:
                                  for f, a, ln in runs), key=lambda r: r[0]) for hx, runs in plan.items()}
         self.buffers = list(buffers)
         self.device = _norm_device(device)
+        # what binding an `into=` record cost (zest_amd.into.IntoRecord.bind); zero for every other set
+        self.seam_chunks, self.seam_bytes, self.bind_s = 0, 0, 0.0
 
     @classmethod
     def from_files(cls, files, device) -> "ResidentSet":
@@ -103,21 +107,32 @@ class ResidentSet:
             if id(b) not in seen:
                 seen.add(id(b))
                 bufs.append(b)
-        return ResidentSet(plan, bufs, self.device)
+        out = ResidentSet(plan, bufs, self.device)
+        out.seam_chunks, out.seam_bytes = self.seam_chunks + other.seam_chunks, self.seam_bytes + other.seam_bytes
+        out.bind_s = self.bind_s + other.bind_s
+        return out
 
 
 def as_resident_set(base, device) -> ResidentSet:
     """The `base=` keyword as one ResidentSet on `device`: a Weights, a ResidentSet, what
-    `zest_amd.publish` returned (a Published) or a list of those.  Raises ValueError for anything
-    else and for a base on another device."""
+    `zest_amd.publish` returned (a Published), what `pull(..., into=...)` returned (a Landed, whose
+    record is bound to its destinations as they are now) or a list of those.  Raises ValueError for
+    anything else and for a base on another device."""
     dev = _norm_device(device)
     items = list(base) if isinstance(base, (list, tuple)) else [base]
     if not items:
         raise ValueError("base= is empty: pass the Weights of an earlier pull (or leave base= out)")
+    from .into import Landed
     from .publish import Published
 
     out = None
     for b in items:
+        if isinstance(b, Landed):
+            if b.device != dev:
+                raise ValueError(f"base= is resident on {b.device} but the pull targets {dev}: a delta pull copies "
+                                 "inside one device; pull the base on that device first (reads from peer GPUs are "
+                                 "not supported)")
+            b = b.record.bind(b, dev)  # fresh: the seam arena is gathered from the destinations as they are
         rs = b.resident if isinstance(b, (zdev.Weights, Published)) else b
         if not isinstance(rs, ResidentSet):
             what = "Weights of a sharded or snapshot pull" if isinstance(b, zdev.Weights) else type(b).__name__
@@ -177,14 +192,17 @@ class _Fetch:
     batches cross file boundaries) into place.  The fetch API wants the jobs' chunks at consecutive
     rows, so they land in a compact table that is then spread over the files' leaf rows.  The tables
     are allocated here and the fetch happens in run(): the caller synchronises the device in between
-    (the pull's private streams must see the allocations) and may queue other work before run()."""
+    (the pull's private streams must see the allocations) and may queue other work before run().
+    dst: the address each run lands at, when that is not its place in its file's buffer (the in-place
+    pull's compact patch, zest_amd.into); `bufs` is then unused."""
 
-    def __init__(self, plans, bufs, which, dev):
+    def __init__(self, plans, bufs, which, dev, dst=None):
         self.plans, self.which, self.dev = plans, which, dev
         self.jobs, self.rows, at = [], [], 0
-        for fi, t0, t1 in which:
+        for k, (fi, t0, t1) in enumerate(which):
             p = plans[fi]
-            self.jobs.append((p.f["xet_hash"], int(t0), int(t1), bufs[fi].data_ptr() + int(p.t_off[t0]), at))
+            to = bufs[fi].data_ptr() + int(p.t_off[t0]) if dst is None else int(dst[k])
+            self.jobs.append((p.f["xet_hash"], int(t0), int(t1), to, at))
             self.rows.append(np.arange(p.leaf0 + p.t_chunk[t0], p.leaf0 + p.t_chunk[t1], dtype=np.int64))
             at += int(p.t_chunk[t1] - p.t_chunk[t0])
         self.fh = torch.zeros((at, 32), dtype=torch.uint8, device=dev)

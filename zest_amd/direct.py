@@ -35,7 +35,9 @@ gather_s.
 but after a group of files verifies `ops.slice_scatter` copies the wanted tensors to the addresses
 of tensors the caller already owns, so nothing but the scratch is allocated (zest_amd.into).
 `cast=True` with it: tensors stored in another float dtype than their destination's (F32, F16, BF16)
-are converted on the way by `ops.slice_scatter_cast`.
+are converted on the way by `ops.slice_scatter_cast`.  `base=` with it (what an earlier `into=` pull
+returned, or any other base): the model is updated in place, only the changed chunks are fetched and
+written, and the rest is verified where it lies.
 """
 from __future__ import annotations
 
@@ -63,9 +65,9 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
         if device == "all":
             raise ValueError("into= is not supported with device='all' (swarm pulls): run one process per GPU with "
                              "device='cuda:N' and that GPU's own destinations")
-        if base is not None:
-            raise ValueError("into= is not supported with base=: nothing records yet which chunks the destinations "
-                             "hold; pull with base= into new tensors, or with into= without a base")
+        if base is not None and cast:
+            raise ValueError("base= is not supported with cast=True: converted destinations do not hold the stored "
+                             "bytes, so nothing of them can be verified or kept; pull with cast=True without a base")
         if seed is not False and seed is not None:
             raise ValueError("into= is not supported with seed=: the file bytes do not stay resident as files; seed "
                              "from a plain device pull")
@@ -81,7 +83,7 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
                              "device='cuda:N' and that GPU's own base")
         if shard is not None:
             raise ValueError("base= is not supported with shard=: a sharded pull keeps no whole file resident to reuse "
-                             "or to serve as the next base; use an unsharded pull")
+                             "or to serve as the next base, and slices do not hold whole chunks; use an unsharded pull")
     if shard is not None:
         if device is None:
             raise ValueError("shard= needs a device: use device='cuda:N' (or 'cpu')")
@@ -101,9 +103,15 @@ def pull_to_device(repo: str, revision: str = "main", device="cuda:0", *, p2p: b
     if into is not None:
         from .into import pull_into
 
+        rs = None
+        if base is not None:  # refusals first; a Landed is bound here, to its destinations as they are now
+            from . import delta as zdelta
+
+            rs = zdelta.as_resident_set(base, dev)
         return pull_into(repo, revision, dev, into, None if shard is None else zshard.as_shard(shard), scratch_bytes,
                          stats, strict, p2p=p2p, peers=peers, tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap,
-                         repo_type=repo_type, staging_bytes=staging_bytes, threads=threads, include=include, cast=cast)
+                         repo_type=repo_type, staging_bytes=staging_bytes, threads=threads, include=include, cast=cast,
+                         base=rs)
     if shard is not None:
         return _pull_sharded(repo, revision, dev, zshard.as_shard(shard), scratch_bytes, stats, p2p=p2p, peers=peers,
                              tracker=tracker, dht=dht, dht_bootstrap=dht_bootstrap, repo_type=repo_type,

@@ -571,6 +571,42 @@ def classify_chunks(seg_lens, chunk_ends) -> dict:
             "seam_chunks": int(seam.sum()), "seam_bytes": int(clen.sum(dtype=np.uint64))}
 
 
+def classify_chunks_with_holes(seg_lens, seg_hole, chunk_ends) -> dict:
+    """`classify_chunks` for a file of which only some segments are in memory.  seg_hole: per segment,
+    True where its bytes are nowhere (a hole).  A chunk that touches a byte of a hole is not resident
+    (`resident[c]` is False): it is no seam chunk, has no pieces and no arena bytes, and its `seg` /
+    `off` mean nothing.  Every other chunk is placed as classify_chunks places it, the seam chunks back
+    to back in an arena of `seam_bytes` bytes that counts resident seam chunks only, so the bound
+    seam_bytes <= 128 KiB * (segment boundaries) still holds."""
+    seg_lens = np.asarray(seg_lens, dtype=np.uint64).reshape(-1)
+    hole = np.asarray(seg_hole, dtype=bool).reshape(-1)
+    if len(hole) != len(seg_lens):
+        raise ValueError("classify_chunks_with_holes: one hole flag per segment")
+    pl = classify_chunks(seg_lens, chunk_ends)
+    ends = np.asarray(chunk_ends, dtype=np.uint64).reshape(-1)
+    starts = np.concatenate([np.zeros(1, np.uint64), ends[:-1]]) if len(ends) else ends
+    vstart = np.cumsum(seg_lens, dtype=np.uint64) - seg_lens
+    hole_len = np.where(hole, seg_lens, np.uint64(0))
+    before = np.cumsum(hole_len, dtype=np.uint64) - hole_len  # hole bytes before each segment
+
+    def hole_bytes_below(p):  # hole bytes in [0, p)
+        s = np.maximum(np.searchsorted(vstart, p, side="right").astype(np.int64) - 1, 0)
+        return before[s] + np.where(hole[s], np.minimum(p - vstart[s], seg_lens[s]), np.uint64(0))
+
+    resident = hole_bytes_below(ends) == hole_bytes_below(starts) if len(ends) else np.zeros(0, dtype=bool)
+    seam = pl["seam"] & resident
+    keep = resident[pl["piece_chunk"]]
+    rows = np.flatnonzero(seam)
+    clen = (ends - starts)[rows]
+    arena_off = np.zeros(len(ends), dtype=np.uint64)
+    arena_off[rows] = np.cumsum(clen, dtype=np.uint64) - clen
+    pc, lo = pl["piece_chunk"][keep], (pl["piece_off"] + vstart[pl["piece_seg"]])[keep]
+    return {"seg": pl["seg"], "off": pl["off"], "seam": seam, "resident": resident,
+            "piece_chunk": pc, "piece_seg": pl["piece_seg"][keep], "piece_off": pl["piece_off"][keep],
+            "piece_len": pl["piece_len"][keep], "piece_dst": arena_off[pc] + (lo - starts[pc]), "arena_off": arena_off,
+            "seam_chunks": int(seam.sum()), "seam_bytes": int(clen.sum(dtype=np.uint64))}
+
+
 class _CallableModule(types.ModuleType):
     """`zest_amd.publish` names this module once it is imported and the function before: calling the
     module publishes, so `zest_amd.publish(files, ...)` works either way."""
